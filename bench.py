@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — whole-step throughput of the hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher environment re-executes itself under torch.distributed.run (one process per GPU,
@@ -745,6 +745,30 @@ def run_micro(a, sim, prog):
     sys.stdout.flush()
 
 
+DUMP_FIELD_BYTES = 48 << 20   # the field sample of --dump-outputs; the block coordinates and max|u| add a few kB
+
+
+def dump_outputs(out_dir, sim, extra_fields, umax_by_step):
+    """--dump-outputs DIR: the state the last timed step handed back, for comparing two builds output for output.  The same whole blocks
+    every run -- chosen by their position in the grid (seeded), not by the library's storage order -- so that the files line up whatever
+    the build:  vel.npy [n][8][8][8][3] and <extra_fields>.npy [n][8][8][8] (float64), blocks.npy [n][3] (block coordinates i, j, k),
+    umax_by_step.npy (max|u| entering every timed step and after the last).  All blocks when they fit in DUMP_FIELD_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    index = np.asarray(sim.grid.index, dtype=np.int64)
+    dims = index.max(axis=0) + 1
+    linear = (index[:, 0] * dims[1] + index[:, 1]) * dims[2] + index[:, 2]
+    order = np.argsort(linear)            # slots in grid-position order
+    n = min(len(order), DUMP_FIELD_BYTES // (512 * 8 * (3 + len(extra_fields))))
+    if n < len(order):
+        order = order[np.sort(np.random.default_rng(2024).choice(len(order), n, replace=False))]
+    slots = order.astype(np.int32)
+    np.save(os.path.join(out_dir, "blocks.npy"), index[slots].astype(np.float64))
+    for field in ["vel"] + list(extra_fields):
+        np.save(os.path.join(out_dir, f"{field}.npy"), sim.download_block_list(field, slots))
+    np.save(os.path.join(out_dir, "umax_by_step.npy"), np.asarray(umax_by_step, dtype=np.float64))
+    sys.stderr.write(f"bench: --dump-outputs: {n} of {len(linear)} blocks ({', '.join(['vel'] + list(extra_fields))}) -> {out_dir}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -788,7 +812,14 @@ def main():
     ap.add_argument("--amr-base", type=int, default=4, help="--amr: uniform starting level (16^3 blocks at 4)")
     ap.add_argument("--amr-levels", type=int, default=3, help="--amr: number of levels of the final mesh")
     ap.add_argument("--amr-fraction", type=float, default=0.3, help="--amr: fraction of the blocks refined per pass")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (velocity, pressure: a fixed sample of whole blocks, "
+                         "float64, <= 64 MB) as DIR/<name>.npy; one process, uniform grid")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and (a.gpus > 1 or a.amr or a.micro):
+        ap.error("--dump-outputs: one process (--gpus 1) and the uniform-grid step (not --amr / --micro)")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and a.gpus > 1:
@@ -958,6 +989,8 @@ def run(a, prog):
     sec = time.perf_counter() - t0
     main_iters = list(iters)
     a.umax_by_step = umax[-a.steps:] + [float(cu.findMaxU(sim))]
+    if a.dump_outputs:   # before anything below touches vel / pres again
+        dump_outputs(a.dump_outputs, sim, [] if a.stencil_only else ["pres"], a.umax_by_step)
     st = RunStats()
     lib().cup3d_stats_read(C.byref(st))
     nit = max(1, st.solver_iterations)

@@ -342,3 +342,42 @@ p.fail("no progress for 5 s in stage 'alt_early'")
     assert hard.returncode != 0
     r = json.loads(hard.stdout.decode().strip().splitlines()[-1])
     assert r["valid"] is False and r["value"] is None and r["stage"] == "alt_early"
+
+
+def test_dump_outputs_sample_is_fixed_by_grid_position_and_under_64_mb(tmp_path):
+    """--dump-outputs at the headline size (64^3 blocks): a seeded sample of whole blocks chosen by their position in the grid, so two
+    builds that store the blocks in different orders write the same files; float64 only, at most 64 MB in all.  No GPU: a stand-in for
+    SimulationData whose 'device' field is a function of the block's position."""
+    import numpy as np
+
+    class Grid:
+        pass
+
+    class Sim:
+        def __init__(self, order):
+            n = 64
+            ijk = np.stack(np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij"), -1).reshape(-1, 3)
+            self.grid = Grid()
+            self.grid.index = ijk[order]
+
+        def download_block_list(self, field, slots):
+            assert slots.dtype == np.int32
+            pos = self.grid.index[slots] @ np.array([4096.0, 64.0, 1.0])
+            shape = (len(slots), 8, 8, 8, 3) if field == "vel" else (len(slots), 8, 8, 8)
+            return np.broadcast_to(pos.reshape((-1,) + (1,) * (len(shape) - 1)) + (1.0 if field == "vel" else 0.5), shape).copy()
+
+    nb = 64 ** 3
+    files = []
+    for k, order in enumerate((np.arange(nb), np.random.default_rng(7).permutation(nb))):
+        d = tmp_path / f"d{k}"
+        bench.dump_outputs(str(d), Sim(order), ["pres"], [1.0, 0.9, 0.8])
+        files.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = files
+    assert sorted(a) == ["blocks.npy", "pres.npy", "umax_by_step.npy", "vel.npy"]
+    assert sum((tmp_path / "d0" / f).stat().st_size for f in a) <= 64 * 10 ** 6
+    n = len(a["blocks.npy"])
+    assert 1000 < n < nb and len(np.unique(a["blocks.npy"], axis=0)) == n
+    assert a["vel.npy"].shape == (n, 8, 8, 8, 3) and a["pres.npy"].shape == (n, 8, 8, 8)
+    for f in a:
+        assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f]), f
+    assert np.array_equal(a["vel.npy"][:, 0, 0, 0, 0], a["blocks.npy"] @ np.array([4096.0, 64.0, 1.0]) + 1.0)   # each block is the one named

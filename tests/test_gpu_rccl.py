@@ -315,3 +315,25 @@ def test_bench_times_the_early_order_as_an_optional_region_that_cannot_lose_the_
     r2 = json.loads(lines[0])
     assert r2["value"] > 0 and r2.get("valid", True) is True and r2["config"]["checksum"]["ok"] is True
     assert "error" in r2["alt_early_allreduce"] and "alt_early" in r2["alt_early_allreduce"]["error"]
+
+
+@pytest.mark.timeout(600)
+def test_dump_outputs_of_the_last_timed_step_repeat_bit_for_bit(tmp_path):
+    """`bench.py --dump-outputs DIR`: what the last timed step left (velocity, pressure; at 64^3 every block) as float64 .npy files,
+    bit-identical over two runs with the same arguments -- the same inputs, the same program -- and `--steps` is the number of timed
+    steps the result line and its per-step arrays report."""
+    import numpy as np
+    args = ("--size", "64", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-alt", "--no-pcie")
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = run_bench(*args, "--dump-outputs", str(d), timeout=400)
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        r = json.loads(out.stdout.decode().strip())
+        assert r["steps"] == 3 and len(r["config"]["bicgstab_iters_by_step"]) == 3 and r["ms_per_step"] > 0
+        runs.append({f: np.load(d / f"{f}.npy") for f in ("vel", "pres", "blocks", "umax_by_step")})
+    a, b = runs
+    assert a["vel"].shape == (512, 8, 8, 8, 3) and a["pres"].shape == (512, 8, 8, 8) and a["blocks"].shape == (512, 3)
+    assert a["umax_by_step"].shape == (4,) and np.isfinite(a["vel"]).all() and np.abs(a["pres"]).max() > 0
+    for f in a:
+        assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f]), f

@@ -536,6 +536,11 @@ __global__ void __launch_bounds__(64) k_debug_wave_sum(const double *__restrict_
   out[threadIdx.x] = wave_sum_mfma(v);
   out[64 + threadIdx.x] = wave_sum(v);
 }
+// TEST SUPPORT: the reciprocal division of the production block CG (cg_div<true>) elementwise: out[i] = fast_div(n[i], d[i])
+__global__ void __launch_bounds__(256) k_debug_cg_div(const double *__restrict__ n, const double *__restrict__ d, long count, double *__restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < count) out[i] = fast_div(n[i], d[i]);
+}
 #endif
 
 static int fdm_setup() {
@@ -625,7 +630,7 @@ int launch_precond(Sim *s, const double *in, double *out, bool want_sums) {
         default: set_error("unknown cg_variant"); return CUP3D_EINVAL;
       }
       break;
-    case 3: CG(true, 0); break;  // alias of 0 (the round-1 kernel IS the production evaluation), kept for old scripts
+    case 3: CG(true, 0); break;  // EV 0: production's evaluation of rounds 1-5 (FMA contraction, IEEE divisions, ds_read2_b64), kept for A/B
     case 4: {  // two blocks per wavefront (A/B timing)
       const int pchunk = ((g.nblocks + 1) / 2 + 7) / 8;
       hipLaunchKernelGGL((k_precond_pair<true, false>), dim3(8 * pchunk), B, 0, stream(), g, pchunk, in, out, sums, 0.0, 0.0, it);
@@ -2277,6 +2282,39 @@ int cup3d_debug_wave_sum(const double *in64, double *out128) {
   }
   hipFree(d);
   if (e != hipSuccess) return hip_fail(e, "cup3d_debug_wave_sum", __FILE__, __LINE__);
+  return CUP3D_OK;
+}
+
+// TEST SUPPORT: see k_debug_cg_div (host arrays of `count` doubles)
+int cup3d_debug_cg_div(const double *n, const double *d, long count, double *out) {
+  if (!n || !d || !out || count < 0 || count > (1L << 30)) return CUP3D_EINVAL;
+  if (count == 0) return CUP3D_OK;
+  const size_t bytes = (size_t)count * sizeof(double);
+  double *b = nullptr;
+  CUP3D_HIP(hipMalloc((void **)&b, 3 * bytes));
+  hipError_t e = hipMemcpy(b, n, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b + count, d, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_debug_cg_div, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream(), b, b + count, count, b + 2 * count);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream());
+    if (e == hipSuccess) e = hipMemcpy(out, b + 2 * count, bytes, hipMemcpyDeviceToHost);
+  }
+  hipFree(b);
+  if (e != hipSuccess) return hip_fail(e, "cup3d_debug_cg_div", __FILE__, __LINE__);
+  return CUP3D_OK;
+}
+
+// TEST SUPPORT: the per-block CG iteration counts behind cup3d_profile_block_cg_iterations (slot order, nblocks of them)
+int cup3d_debug_block_cg_iterations(cup3d_sim_t *h, int32_t *per_block) {
+  if (!h || !per_block) return CUP3D_EINVAL;
+  Sim *s = reinterpret_cast<Sim *>(h);
+  if (!s->d_cg_iters) {
+    set_error("cup3d_debug_block_cg_iterations: no block-CG launch was made on this sim while cup3d_profile_enable(1) was on");
+    return CUP3D_ESTATE;
+  }
+  CUP3D_HIP(hipStreamSynchronize(stream()));
+  CUP3D_HIP(hipMemcpy(per_block, s->d_cg_iters, (size_t)s->nb * sizeof(int), hipMemcpyDeviceToHost));
   return CUP3D_OK;
 }
 #endif

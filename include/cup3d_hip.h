@@ -228,12 +228,13 @@ typedef struct {
   int max_restarts;    /* 100  (main.cpp:14374) */
   int block_solver;    /* how the block preconditioner M^-1 (getZImplParallel, 14704-14745) is evaluated:
                           0 = the reference's block-local CG, iteration for iteration, as the device evaluates it fastest: a*b+c
-                              contracted to FMA (wave-wide sums by DPP reductions, IEEE divisions).  Differs from the reference's z
+                              contracted to FMA (wave-wide sums by DPP reductions, divisions by v_rcp_f64 + Newton steps, within
+                              1 ulp of IEEE).  Differs from the reference's z
                               by less than the CG's own 1e-7 truncation (tests: measured against block_solver 2 and the reference);
                           1 = direct block solve by fast diagonalisation (same operator, exact to rounding);
                           2 = the block CG in the reference's association: no FMA contraction (only the ORDER of the 512-term sums
                               differs from the CPU); slower, for parity checks;
-                          3, 4 = A/B timing variants (3: alias of 0; 4: two blocks per wavefront), libcup3d_hip_testing.so only;
+                          3, 4 = A/B timing variants (3: 0's evaluation of rounds 1-5, IEEE divisions; 4: two blocks per wavefront), libcup3d_hip_testing.so only;
                           5 = NOT the reference's preconditioner: one geometric-multigrid V(2,2)-cycle (red-black Gauss-Seidel in LDS,
                               summed-residual restriction, piecewise-constant prolongation) on the hierarchy of uniform block grids --
                               same operator, same stopping rule, same converged pressure to solver tolerance, O(10) instead of O(150)

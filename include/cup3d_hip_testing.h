@@ -20,6 +20,11 @@ CUP3D_API int cup3d_debug_virtual_comm(int nranks);
 CUP3D_API int cup3d_debug_advdiff_stage(cup3d_sim_t *, int rk, double dt, double nu, const double uinf[3]);
 CUP3D_API int cup3d_debug_amr_slabs(cup3d_sim_t *, int field, int w, double *out);
 CUP3D_API int cup3d_debug_wave_sum(const double *in64, double *out128);
+/* fast_div, the reciprocal division of the production block CG (v_rcp_f64, two Newton steps, one residual correction), elementwise:
+ * out[i] = n[i] / d[i] within 1 ulp; host arrays */
+CUP3D_API int cup3d_debug_cg_div(const double *n, const double *d, long count, double *out);
+/* per-block CG iterations of the last block-CG launch made on this sim while cup3d_profile_enable(1) was on (slot order; nblocks values) */
+CUP3D_API int cup3d_debug_block_cg_iterations(cup3d_sim_t *, int32_t *per_block);
 /* the solver's scalar recurrences (SolverCtl, poisson.hip) stepped on the host -- the same functions the device runs; no GPU needed.
  * io[16] = alpha, beta, omega, r0r_prev, norm, init_norm, min_norm, tol, tol_rel, state (0 run, 1 done, 2 restart), restarts,
  * max_restarts, xcur, xopt, iter; step 1 takes totals[2] (main.cpp:14493), step 2 totals[7] (14558-14601) */

@@ -75,6 +75,8 @@ def lib():
     L.orc_advdiff_stage_rhs.argtypes = [vp, _dp, _dp, C.c_double, C.c_double, _dp]
     L.orc_lhs.argtypes = [vp, _dp, _dp, C.c_int]
     L.orc_precond.argtypes = [vp, _dp]
+    L.orc_precond_block_coef.restype = C.c_long
+    L.orc_precond_block_coef.argtypes = [_dp, C.c_double, C.c_double]
     L.orc_solve.argtypes = [vp, _dp, _dp, C.POINTER(SolveInfo)]
     L.orc_pressure_rhs.argtypes = [vp, _dp, _dp, _dp, _dp, C.c_double]
     L.orc_div_pressure.argtypes = [vp, _dp, _dp]
@@ -402,6 +404,18 @@ class OracleMesh:
         out = np.zeros((self.nb, 27), dtype=np.int32)
         lib().orc_mesh_states(self.m, out)
         return out
+
+
+def precond_blocks(rhs, h, centre=-6.0):
+    """getZImplParallel block by block (orc_precond_block_coef: the reference's block CG, main.cpp:14704-14745 / 10534-10579) on
+    rhs[n,8,8,8] with a scalar or per-block h and centre coefficient; returns (z, CG iterations per block)."""
+    z = np.array(rhs, dtype=np.float64, order="C", copy=True)
+    n = len(z)
+    hs, cs = np.broadcast_to(np.asarray(h, dtype=np.float64), (n,)), np.broadcast_to(np.asarray(centre, dtype=np.float64), (n,))
+    its = np.zeros(n, dtype=np.int64)
+    for b in range(n):
+        its[b] = lib().orc_precond_block_coef(z[b], float(hs[b]), float(cs[b]))  # in place
+    return z, its
 
 
 def restrict_field(fine, coarse, field):

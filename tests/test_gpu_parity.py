@@ -785,13 +785,12 @@ def test_mean_constraint_3_against_the_reference(golden_dir):
         assert_two_valid_iterates(o, g.index, sim.download("pres"), z["pr_pres"], tau_of(r), sim.download("vel"), z["pr_vel"], float(z["dt"]), g.h)
 
 
-@pytest.mark.parametrize("level,bc", [(3, ("wall",) * 3), (4, ("wall",) * 3), (3, ("freespace", "wall", "periodic"))])
-def test_solver_runs_ahead_of_the_host_across_restarts_and_refreshes(level, bc):
-    """All-wall Taylor-Green, three projections from step 21: 70-120 BiCGSTAB iterations each, i.e. runs of fused iterations whose
-    scalars never leave the device (SolverCtl, poisson.hip) interrupted by the host-driven every-50th iterations, and serious
-    breakdowns (the oracle restarts in several of these solves) that the device reports one iteration after the host enqueued the
-    next one.  Iteration counts: the WINDOW of the three solves within 15 % of the oracle's, every returned iterate within the stopping rule's bound; the same
-    solves with the host-driven loops (`no_fuse`) agree with the fused ones in count (same arithmetic, other summation order)."""
+RUN_AHEAD_CASES = [(3, ("wall",) * 3), (4, ("wall",) * 3), (3, ("freespace", "wall", "periodic"))]
+
+
+def _run_ahead_case(level, bc):
+    """The three projections of one case of test_solver_runs_ahead_of_the_host_across_restarts_and_refreshes, with the assertions per
+    solve; returns the case's iteration window and whether a restart was seen."""
     ext = 2 * np.pi
     o = O.OracleGrid((1, 1, 1), level + 1, level, ext, bc)
     sim = cu.SimulationData(bpdx=1, bpdy=1, bpdz=1, levelMax=level + 1, levelStart=level, extent=ext, nu=0.01, BC_x=bc[0], BC_y=bc[1], BC_z=bc[2])
@@ -833,6 +832,37 @@ def test_solver_runs_ahead_of_the_host_across_restarts_and_refreshes(level, bc):
         print(f"    host-driven unfused loops: {r2.iterations} its / {r2.restarts} restarts")
         assert_two_valid_iterates(o, o.index, s2.download("pres"), rp, tau_of(r2))
         del s2
+    return window, seen_restart
+
+
+@pytest.fixture(scope="module")
+def run_ahead_cases():
+    """The run-ahead cases, each computed once per module whichever of the two tests below asks first (-k, -x, reordering): a case that
+    raised keeps its exception, which its own test re-raises, and is not run again."""
+    done = {}
+
+    def get(level, bc):
+        key = (level, tuple(bc))
+        if key not in done:
+            try:
+                done[key] = (_run_ahead_case(level, bc), None)
+            except Exception as e:  # noqa: BLE001 -- recorded, raised by the case's own test
+                done[key] = (None, e)
+        return done[key]
+    return get
+
+
+@pytest.mark.parametrize("level,bc", RUN_AHEAD_CASES)
+def test_solver_runs_ahead_of_the_host_across_restarts_and_refreshes(level, bc, run_ahead_cases):
+    """All-wall Taylor-Green, three projections from step 21: 70-120 BiCGSTAB iterations each, i.e. runs of fused iterations whose
+    scalars never leave the device (SolverCtl, poisson.hip) interrupted by the host-driven every-50th iterations, and serious
+    breakdowns (the oracle restarts in several of these solves) that the device reports one iteration after the host enqueued the
+    next one.  Iteration counts: the WINDOW of the three solves within 15 % of the oracle's, every returned iterate within the stopping rule's bound; the same
+    solves with the host-driven loops (`no_fuse`) agree with the fused ones in count (same arithmetic, other summation order)."""
+    result, error = run_ahead_cases(level, bc)
+    if error is not None:
+        raise error
+    window, seen_restart = result
     # the window: the three solves together, device (fused and host-driven) against the oracle restarted from the device's state each step.
     # Recorded spreads of the sums over round 5's runs: -11 % ... +5 %; SURVEY 8c's +-10 % is what ONE summation order of the reference
     # itself does not keep from run to run (166 / 196 on one 512^3 step), so the band here is 15 %.
@@ -841,24 +871,25 @@ def test_solver_runs_ahead_of_the_host_across_restarts_and_refreshes(level, bc):
     # cases of this module run -- nine solves -- within 10 % (test_pooled_iteration_window_of_the_run_ahead_cases)
     for k in ("device", "host_driven"):
         assert abs(window[k] - window["oracle"]) <= 0.25 * window["oracle"] + 3, window
-    for k, v in window.items():
-        POOLED_WINDOW[k] = POOLED_WINDOW.get(k, 0) + v
-    POOLED_WINDOW["cases"] = POOLED_WINDOW.get("cases", 0) + 1
     assert seen_restart or level == 3
 
 
-POOLED_WINDOW = {}
-
-
-def test_pooled_iteration_window_of_the_run_ahead_cases():
+def test_pooled_iteration_window_of_the_run_ahead_cases(run_ahead_cases):
     """iteration count within +-10 % of the reference's -- as a statement about a WINDOW (nine solves on three grids, each against
     the oracle restarted from the device's own state), because one solve of this BiCGSTAB moves by 20-40 % with the order of its sums on
     either side (the multi-threaded reference's own: 166 / 196 on one 512^3 step).  Round 6, one run: device 690, host-driven 667, oracle 663."""
-    if POOLED_WINDOW.get("cases", 0) < 3:
-        pytest.skip("needs the three cases of test_solver_runs_ahead_of_the_host_across_restarts_and_refreshes in the same session")
-    print(f"pooled over {POOLED_WINDOW['cases']} cases: {POOLED_WINDOW}")
+    pooled = {"cases": 0}
+    for level, bc in RUN_AHEAD_CASES:
+        result, _ = run_ahead_cases(level, bc)
+        if result is None:
+            continue
+        for k, v in result[0].items():
+            pooled[k] = pooled.get(k, 0) + v
+        pooled["cases"] += 1
+    assert pooled["cases"] == 3, f"only {pooled['cases']} of the three run-ahead cases produced a window (their own tests say why)"
+    print(f"pooled over {pooled['cases']} cases: {pooled}")
     for k in ("device", "host_driven"):
-        assert abs(POOLED_WINDOW[k] - POOLED_WINDOW["oracle"]) <= 0.10 * POOLED_WINDOW["oracle"], POOLED_WINDOW
+        assert abs(pooled[k] - pooled["oracle"]) <= 0.10 * pooled["oracle"], pooled
 
 
 def test_iteration_cap_and_status_ring():

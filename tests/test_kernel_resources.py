@@ -31,7 +31,7 @@ def test_every_translation_unit_carries_gfx950_code(release):
 
 
 def test_fused_solver_kernels(release):
-    """k_loop1_cg / k_loop2_cg_w4 <FMA, EV = 0, FLHS = true>: the two launches of a BiCGSTAB iteration on uniform grids"""
+    """k_loop1_cg / k_loop2_cg_w4 <FMA, EV = 6 (kCgProduction), FLHS = true>: the two launches of a BiCGSTAB iteration on uniform grids"""
     l1, l2 = release["k_loop1_cg<b1,i6,b1>"], release["k_loop2_cg_w4<b1,i6,b1>"]
     for k in (l1, l2):
         assert k["scratch_bytes"] == 0 and k["vgpr_spills"] == 0 and k["agpr"] == 0, k
@@ -47,7 +47,7 @@ def test_fused_solver_kernels(release):
 
 
 def test_fused_solver_kernels_with_the_totals_inside(release):
-    """k_loop1_cg_tot / k_loop2_cg_tot <FMA, EV = 0>: the same two kernels totalling their per-block values themselves (Arrive, poisson.hip) --
+    """k_loop1_cg_tot / k_loop2_cg_tot <FMA, EV = 6 (kCgProduction)>: the same two kernels totalling their per-block values themselves (Arrive, poisson.hip) --
     the early all-reduce over ranks (CUP3D_EARLY_ALLREDUCE=1).  The arrival code sits behind the plane loop; the second kernel is HELD to 128
     registers (the compiler would take 136 -> 3 wavefronts per SIMD): one 8-byte value is parked in scratch before the plane loop and fetched
     back when the block CG starts -- never inside a loop (the ISA's only scratch accesses: one store pair up front, one load pair behind

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — whole-step throughput of the hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher environment re-executes itself under torch.distributed.run (one process per GPU,
@@ -19,7 +19,13 @@ path, no adaptMesh step).  Fields are resident in HBM before the timed region.
 Prints ONE JSON line (rank 0): metric Mcell-updates/s = cells * steps / seconds over all
 ranks (strong scaling: the grid is fixed, blocks are sharded by Hilbert ranges), plus
 `roofline` (dominant kernel by device time, algorithmic bytes / measured kernel time vs
-8 TB/s) and `cpu_baseline` (the compiled reference on this host's cores, bounded sample).
+8 TB/s, from the per-kernel events of the timed steps themselves).
+
+A plain run does only what that line needs: set up, warm up, time the K steps, write --dump-outputs, print.  Everything else
+the bench measures or checks runs with --full only, after the timed steps (config.checksum before them): config.checksum,
+config.ref_iters_per_step, `stencil_only` (metric A), `pcie_inclusive`, `alt` / `alt_multigrid` / `alt_reference_association`,
+`alt_early_allreduce` (N > 1) and `cpu_baseline` (the compiled reference on this host's cores, bounded sample).  --no-checksum,
+--no-alt, --no-alt-early, --no-pcie and --no-cpu trim a --full run.
 
 A run over N > 1 ranks cannot end silently: every rank reports its stage (rendezvous, comm_init, checksum, warmup, timed, ...) to a
 progress file, a watchdog thread per rank (and the self-launching parent) ends the run when a stage stalls (--stall-timeout) or the
@@ -779,6 +785,9 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=5, help="steps of the CPU-baseline sample; the median step is reported (SURVEY 8d: >= 5 repeats)")
     ap.add_argument("--cpu-threads", type=int, default=32,
                     help="OpenMP threads of the reference; 32 is its best on the 256-thread GPU host (see report()); 0: all host cores")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: config.checksum, the reference's recorded iteration counts, metric (A), "
+                         "the PCIe-inclusive rates, the other block preconditioners, the early all-reduce order (N > 1) and the CPU baseline")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--stencil-only", action="store_true", help="BASELINE configs[1]: periodic, advect-diffuse only")
     ap.add_argument("--block-solver", type=int, default=0, help="0: block CG as in the reference, 1: direct block solve, 5: multigrid V-cycle")
@@ -936,7 +945,7 @@ def run(a, prog):
                             BC_x=bc, BC_y=bc, BC_z=bc, uMax_forced=1.0, rampup=0, rank=rank, nranks=world, blockSolver=a.block_solver,
                             implicitDiffusion=a.implicit_diffusion)
     a.checksum = None
-    if not a.stencil_only and not a.implicit_diffusion and not a.no_checksum and not a.micro:
+    if a.full and not a.stencil_only and not a.implicit_diffusion and not a.no_checksum and not a.micro:
         stage("checksum", "first exchanges over the transport: advect-diffuse, LHS, one fused iteration")
         a.checksum = advdiff_checksums(sim, a, dist, world, prog)  # the run's correctness signal at every N (before anything is timed)
         sim.dt = 0.0
@@ -1030,7 +1039,7 @@ def run(a, prog):
     # --stencil-only --size 256) -- five operator calls after the timed region, so `value` never sees them.  The velocity it leaves
     # behind is not used again (every `alt` region uploads the initial condition).
     a.stencil_sub = None
-    if not a.stencil_only and not a.implicit_diffusion:
+    if a.full and not a.stencil_only and not a.implicit_diffusion:
         stage("alt", "SURVEY 8(d) metric (A): the RK3 operator alone")
         nrk = 5
         adv(sim.dt)   # (untimed: the first call after the projection)
@@ -1063,7 +1072,7 @@ def run(a, prog):
     # that very path (cup3d_sim_upload_blocks / _download_blocks on resident, reused host pages), then applied to the bytes the shim
     # moves per step in its two modes
     a.pcie = None
-    if world == 1 and not a.stencil_only and not a.implicit_diffusion and not a.no_pcie:
+    if a.full and world == 1 and not a.stencil_only and not a.implicit_diffusion and not a.no_pcie:
         fid = cu.operators.FIELDS["vel"]
         hv = np.empty((sim.nblocks, 8, 8, 8, 3))
         ptrs = (C.c_void_p * sim.nblocks)(*[hv[i].ctypes.data for i in range(sim.nblocks)])
@@ -1091,7 +1100,7 @@ def run(a, prog):
     SOLVERS = {0: "block CG (reference algorithm)", 1: "direct block solve (fast diagonalisation)", 2: "block CG, reference association (no FMA)",
                5: "geometric multigrid V(2,2)-cycle (NOT the reference's preconditioner; same operator, stopping rule and converged pressure)"}
     alt, alts = None, {}
-    if not a.stencil_only and not a.no_alt and not a.implicit_diffusion and world == 1:
+    if a.full and not a.stencil_only and not a.no_alt and not a.implicit_diffusion and world == 1:
         # the same workload once more with the preconditioner M^-1 evaluated / chosen differently (cup3d_poisson_params.block_solver),
         # reported NEXT to the headline, never instead of it: the direct block solve (the reference's M, exact instead of by CG) and,
         # a multigrid V-cycle in M's place (what BASELINE.json's north_star wording describes; the reference has none; over several
@@ -1155,7 +1164,7 @@ def run(a, prog):
     # the one every multi-rank test has run; this region is OPTIONAL: if it fails or hangs, the watchdog prints the main result with
     # alt_early_allreduce = {"error": ...} instead of losing the run.
     a.alt_early = None
-    if (world > 1 and a.transport == "rccl" and not a.stencil_only and not a.implicit_diffusion and a.block_solver == 0 and not a.no_alt_early
+    if (a.full and world > 1 and a.transport == "rccl" and not a.stencil_only and not a.implicit_diffusion and a.block_solver == 0 and not a.no_alt_early
             and not os.environ.get("CUP3D_EARLY_ALLREDUCE") and not invalid):
         def fallback(error, rank_progress):
             a.alt_early = {"error": error, "rank_progress": rank_progress}
@@ -1249,6 +1258,7 @@ def report(a, sim, prof, sec, iters, world, alt=None):
     cells = float(a.size) ** 3
     cells_local = sim.nblocks * 512.0
     value = cells * a.steps / sec / 1e6
+    full = getattr(a, "full", False)   # (the side records of --full; a plain run prints what the headline needs)
     kernels = []
     total_ms = sum(ms for _, ms in prof.values()) or 1.0
     traffic = traffic_record()
@@ -1302,7 +1312,7 @@ def report(a, sim, prof, sec, iters, world, alt=None):
                    # max|u| entering every timed step and after the last one: a solver-level signal that must not depend on the number
                    # of ranks beyond the stopping tolerance of the projection (the checksum below covers the stencil path bit for bit)
                    "umax_by_step": getattr(a, "umax_by_step", None),
-                   "ref_iters_per_step": ref_iters(a, iters),
+                   "ref_iters_per_step": ref_iters(a, iters) if full else None,
                    "checksum": getattr(a, "checksum", None),
                    "communication": getattr(a, "comm", None),
                    "nu": a.nu, "implicit_diffusion": bool(a.implicit_diffusion),
@@ -1336,7 +1346,7 @@ def report(a, sim, prof, sec, iters, world, alt=None):
         out["communication_stream"] = a.comm_entries
     if getattr(a, "pcie", None):
         out["pcie_inclusive"] = a.pcie
-    if not a.no_cpu and world == 1:
+    if full and not a.no_cpu and world == 1:
         # SURVEY 8d asks for the reference on all host cores at 512^3, else 256^3.  A 512^3 step of the reference takes 4.5 minutes
         # (268 s for the projection alone on 64 threads, profiles/r02/reference_step_512.json) and ~35 GB: the sample is the MEDIAN of
         # --cpu-steps (5) separate steps at 256^3.  "All cores" would be a strawman on this host: the reference's OpenMP regions (one lab per thread, master-polled halo
@@ -1346,7 +1356,7 @@ def report(a, sim, prof, sec, iters, world, alt=None):
         threads = min(a.cpu_threads or (os.cpu_count() or 1), os.cpu_count() or 1)
         out["cpu_baseline"] = cpu_baseline(a.cpu_size, a.cpu_steps, threads, stencil_only=a.stencil_only)
         out["cpu_baseline"]["host_cores_available"] = os.cpu_count()
-    if not a.no_cpu and world == 1 and not a.stencil_only:
+    if full and not a.no_cpu and world == 1 and not a.stencil_only:
         # the all-core figure SURVEY 8d asks for, quoted from the recorded scan (one step takes 5.6 minutes there: not re-run here)
         out["cpu_baseline"]["all_cores_recorded"] = {"value": round(256 ** 3 / 338.49 / 1e6, 4), "unit": "Mcell-updates/s", "cores": 256, "size": 256,
                                                      "also": {"64 threads": round(256 ** 3 / 30.31 / 1e6, 3), "32 threads": round(256 ** 3 / 18.17 / 1e6, 3)},

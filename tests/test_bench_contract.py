@@ -34,6 +34,29 @@ def test_help_runs_without_a_gpu():
     assert b"--gpus" in out.stdout and b"--steps" in out.stdout and b"--warmup" in out.stdout
 
 
+def test_plain_run_leaves_the_side_records_to_full(monkeypatch):
+    """A plain run prints what the headline needs; the CPU baseline and the reference's recorded iteration counts come with --full only
+    (the regions run() gates the same way -- checksum, metric A, PCIe, the other preconditioners -- need a GPU: tests/test_gpu_rccl.py)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, check=True, timeout=120)
+    assert b"--full" in out.stdout
+    calls = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *args, **kw: calls.append("cpu") or {"value": 1.0, "unit": "Mcell-updates/s", "sample": "stub"})
+    monkeypatch.setattr(bench, "ref_iters", lambda *args: calls.append("ref") or {"value": 170.0})
+    prof = {"bicgstab_loop2_cg": (762, 762 * 3.9), "bicgstab_loop1_cg": (762, 762 * 3.8)}
+    lines = {}
+    for full in (False, True):
+        buf = io.StringIO()
+        with redirect_stdout(buf):
+            bench.report(_args(no_cpu=False, full=full), _Sim(), prof, 7.4, [156] * 5, 1)
+        lines[full] = json.loads(buf.getvalue().strip())
+        assert calls == (["ref", "cpu", "cpu"] if full else []), (full, calls)
+    plain, full = lines[False], lines[True]
+    assert "cpu_baseline" not in plain and plain["config"]["ref_iters_per_step"] is None
+    assert full["cpu_baseline"]["value"] == 1.0 and full["config"]["ref_iters_per_step"] == {"value": 170.0}
+    for k in ("value", "ms_per_step", "roofline", "kernels"):
+        assert plain[k] == full[k], k
+
+
 def test_report_emits_the_contract():
     prof = {"bicgstab_loop2_cg": (762, 762 * 3.9), "bicgstab_loop1_cg": (762, 762 * 3.8), "poisson_lhs": (1667, 1667 * 0.53), "project_pointwise": (20, 14.0)}
     buf = io.StringIO()

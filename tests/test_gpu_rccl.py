@@ -34,13 +34,14 @@ def same_bits_at_every_n(ck1, ckn):
 FAKE_RCCL = os.path.join(ROOT, "tests", "fake_rccl", "librccl_fake.so")
 
 
-def run_bench(*args, timeout=900, extra_env=None, alt_early=False):
+def run_bench(*args, timeout=900, extra_env=None, alt_early=False, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env or {})
+    # --full: these tests read what a plain run leaves out (config.checksum, ref_iters_per_step, the optional regions)
     # --full-line: these tests read the full record (checksum values, per-step arrays); the default stdout line is the compact summary
     # --no-alt-early: the optional early-all-reduce region of N > 1 runs has its own test below
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line", "--detail-out", "", *([] if alt_early else ["--no-alt-early"]), *args], env=env,
-                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *(["--full"] if full else []), "--full-line", "--detail-out", "",
+                           *([] if alt_early else ["--no-alt-early"]), *args], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
 
 
 def test_one_process_bench_carries_a_matching_checksum():
@@ -337,3 +338,30 @@ def test_dump_outputs_of_the_last_timed_step_repeat_bit_for_bit(tmp_path):
     assert a["umax_by_step"].shape == (4,) and np.isfinite(a["vel"]).all() and np.abs(a["pres"]).max() > 0
     for f in a:
         assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f]), f
+
+
+@pytest.mark.timeout(600)
+def test_a_plain_run_times_the_same_steps_as_a_full_run(tmp_path):
+    """`bench.py` without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- no checksum pass before the timed
+    steps, nothing measured after them.  What the last timed step computed is the same bits as in a --full run (whose checksum pass
+    runs on the same fields first), and the line carries the timed region's figures but none of the side records."""
+    import numpy as np
+    args = ("--size", "64", "--steps", "3", "--warmup", "1")
+    runs, lines = [], []
+    for k, full in enumerate((False, True)):
+        d = tmp_path / f"run{k}"
+        out = run_bench(*args, *(("--no-cpu",) if full else ()), "--dump-outputs", str(d), full=full, timeout=400)
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        lines.append(json.loads(out.stdout.decode().strip()))
+        runs.append({f: np.load(d / f"{f}.npy") for f in ("vel", "pres", "blocks", "umax_by_step")})
+    plain, full = lines
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["roofline"]["frac"] > 0
+    assert plain["config"]["bicgstab_iters_by_step"] == full["config"]["bicgstab_iters_by_step"]
+    assert plain["config"]["checksum"] is None and plain["config"]["ref_iters_per_step"] is None
+    for k in ("stencil_only", "pcie_inclusive", "alt", "alt_multigrid", "alt_reference_association", "cpu_baseline"):
+        assert k not in plain, k
+    assert full["config"]["checksum"]["ok"] is True
+    for k in ("stencil_only", "pcie_inclusive", "alt", "alt_multigrid", "alt_reference_association"):
+        assert k in full, k

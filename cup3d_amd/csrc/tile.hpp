@@ -64,16 +64,6 @@ __device__ __forceinline__ double wave_sum(double v) {
   v += dpp_move_rows<0x143, 0xc>(v, t5);                // row_bcast31 into rows 2 and 3: lane 63 = (R3 + R2) + (R1 + R0)
   return broadcast_lane63(v);
 }
-// rounds 1-5's form of the two cross-row steps (old = 0: two v_mov_b32 0 and a nop per step) -- kept for the A/B (EV bit 64 of cg_block)
-__device__ __forceinline__ double wave_sum_zero_old(double v) {
-  v += dpp_move<0xB1>(v);
-  v += dpp_move<0x4E>(v);
-  v += dpp_move<0x141>(v);
-  v += dpp_move<0x140>(v);
-  v += dpp_move<0x142, 0xa>(v);
-  v += dpp_move<0x143, 0xc>(v);
-  return broadcast_lane63(v);
-}
 __device__ __forceinline__ double wave_max(double v) {
   v = fmax(v, dpp_move<0xB1>(v));
   v = fmax(v, dpp_move<0x4E>(v));
@@ -83,6 +73,18 @@ __device__ __forceinline__ double wave_max(double v) {
   for (int m = 32; m >= 16; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
   return v;
 }
+
+// ---- values handed from one wavefront to another inside a launch (the in-kernel totals of the Poisson solver, poisson_totals.hpp).
+// Everything one wavefront hands to another inside a launch -- per-block values, group sums, counters, totals, flags -- travels by
+// AGENT-scope atomic stores / loads / read-modify-writes (sc1 on gfx950: written through and read past the per-XCD L2s, which are not
+// coherent with one another), ordered by s_waitcnt alone (a workgroup-scope fence).  NOT by __threadfence(): an agent-scope release fence is
+// a write-back of the XCD's whole L2 (buffer_wbl2), there to publish ORDINARY stores that may sit dirty in it -- one per wavefront, 262 144
+// per launch, made the loop kernels seven times slower (3.4 instead of 0.5 ms at 256^3).  No ordinary store is published here.
+__device__ __forceinline__ double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_agent(unsigned *p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// this lane's agent-scope stores have completed (they are write-through: complete = visible to the agent) before anything that follows
+__device__ __forceinline__ void stores_done() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); }
 
 // workgroup sum for blockDim.x == 64 * NW; result valid in every thread
 template <int NW>

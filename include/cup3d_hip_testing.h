@@ -25,7 +25,7 @@ CUP3D_API int cup3d_debug_wave_sum(const double *in64, double *out128);
 CUP3D_API int cup3d_debug_cg_div(const double *n, const double *d, long count, double *out);
 /* per-block CG iterations of the last block-CG launch made on this sim while cup3d_profile_enable(1) was on (slot order; nblocks values) */
 CUP3D_API int cup3d_debug_block_cg_iterations(cup3d_sim_t *, int32_t *per_block);
-/* the solver's scalar recurrences (SolverCtl, poisson.hip) stepped on the host -- the same functions the device runs; no GPU needed.
+/* the solver's scalar recurrences (SolverCtl, poisson_ctl.hpp) stepped on the host -- the same functions the device runs; no GPU needed.
  * io[16] = alpha, beta, omega, r0r_prev, norm, init_norm, min_norm, tol, tol_rel, state (0 run, 1 done, 2 restart), restarts,
  * max_restarts, xcur, xopt, iter; step 1 takes totals[2] (main.cpp:14493), step 2 totals[7] (14558-14601) */
 CUP3D_API int cup3d_debug_ctl_step(int step, double *io, const double *totals);

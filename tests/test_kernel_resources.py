@@ -3,6 +3,7 @@ per SIMD, LDS -> workgroups per CU, scratch.  DESIGN.md section 4 argues with th
 fused BiCGSTAB kernels with the LHS inside, 5 for the block CG, three 48.8 KB advect-diffuse workgroups per CU); this keeps them true, and
 keeps register spills from creeping into a hot loop unnoticed when a kernel is edited.  `python scripts/kernel_resources.py` prints the table."""
 import os
+import re
 import sys
 
 import pytest
@@ -111,3 +112,9 @@ def test_release_build_has_no_tuning_variants_of_the_block_cg():
     assert any(n.startswith("k_precond") for n in extra), sorted(extra)[:10]
     # measured and dropped (profiles/README.md): test builds only
     assert not any(n.startswith(("k_advdiff_c", "k_advdiff_pc", "k_debug")) or n in ("k_loop2_cg<b1,i6,b1>", "k_loop2_cg_w4<b1,i6,b0>") for n in rel), sorted(rel)
+    # retired experiments (dummy streams, single-reduction block CG, wave sums through LDS / with zero moves): in no build any more;
+    # what is left of the block CG's evaluations is the four bits 1, 2, 4, 8
+    assert not any(n.startswith(("k_loop1_cg_x", "k_loop2_cg_x", "k_loop2_cg_w4f")) for n in tst), sorted(tst)
+    ev = {n: re.search(r"[<,]i(\d+)[,>]", n) for n in tst if n.startswith(("k_precond<", "k_loop1_cg", "k_loop2_cg"))}  # EV: their one integer argument
+    assert all(ev.values()) and {n.split("<")[0] for n in ev} >= {"k_precond", "k_loop1_cg", "k_loop2_cg", "k_loop2_cg_w4"}, sorted(ev)
+    assert all(0 <= int(m.group(1)) <= 15 for m in ev.values()), sorted(n for n, m in ev.items() if not 0 <= int(m.group(1)) <= 15)

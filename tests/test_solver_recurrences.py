@@ -1,5 +1,5 @@
 """The scalar recurrences of the pipelined BiCGSTAB (PoissonSolverAMR::solve, main.cpp:14493, 14558-14601) as the product evaluates them:
-ONE pair of functions (ctl_step1 / ctl_step2, poisson.hip) compiled for host and device -- on the device they run in the kernel that
+ONE pair of functions (ctl_step1 / ctl_step2, poisson_ctl.hpp) compiled for host and device -- on the device they run in the kernel that
 totals the dot products, so the host never sits on the solver's critical path.  Here their HOST compilation (cup3d_debug_ctl_step, no
 GPU needed) is compared with a line-by-line restatement of the reference's statements in IEEE double arithmetic (numpy float64 scalars:
 every operation rounded once, like the reference's x86-64 baseline build), bit for bit, over random and adversarial inputs: both branches

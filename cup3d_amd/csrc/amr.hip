@@ -15,6 +15,7 @@
 //     down (FillCoarseVersion 4171-4235), domain faces mirrored (_apply_bc on the coarse tile, 3781).
 // After the kernel, k_flux_fix applies FluxCorrectionMPI::FillBlockCases (2825-2935) to the coarse side.
 // All arithmetic keeps the reference's association (-ffp-contract=off): results are bit-identical to it.
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 
@@ -893,38 +894,45 @@ extern "C" int cup3d_adapt_migrate(const cup3d_grid_t *old_mesh_h, const int32_t
 // the resident chi; with cup3d_compute_vorticity before and cup3d_tag_blocks after it, adaptMesh's decision input is complete for
 // runs with obstacles.  `mo`: a multi-level mesh object whose first `nloc` slots are the blocks of `tmpV` (the mesh itself on one
 // rank, the rank's TENSORIAL view over ranks -- the tensorial chi tile reaches edge / corner neighbours); `chi` lives on mo's slots.
+// The finer leaves behind every kNbrFiner position of the blocks [0, nloc) of `mo`, by octant of the block (bits of x, y, z >= 4):
+// finer_row[b] = the block's row of finer[rows][27][8] (-1: no finer neighbour), -1 in the row where nothing is read.  Throws what
+// Grid::leaf throws.
+static void finer_tables(const Grid *mo, int64_t nloc, std::vector<int32_t> &finer_row, std::vector<int32_t> &finer) {
+  finer_row.assign((size_t)nloc, -1);
+  for (int64_t b = 0; b < nloc; ++b) {
+    bool any = false;
+    for (int c = 0; c < 27; ++c) any = any || mo->nbr27[27 * (size_t)b + c] == kNbrFiner;
+    if (!any) continue;
+    finer_row[b] = (int32_t)(finer.size() / 216);
+    finer.resize(finer.size() + 216, -1);
+    int32_t *row = finer.data() + finer.size() - 216;
+    const int l = mo->blevel[b];
+    for (int icode = 0; icode < 27; ++icode) {
+      if (mo->nbr27[27 * (size_t)b + icode] != kNbrFiner) continue;
+      const int code[3] = {icode % 3 - 1, (icode / 3) % 3 - 1, icode / 9 - 1};
+      for (int q = 0; q < 8; ++q) {
+        int fi[3];
+        bool used = true;
+        for (int d = 0; d < 3; ++d) {
+          const int bit = (q >> d) & 1;
+          if (code[d] != 0 && bit) used = false;
+          fi[d] = 2 * mo->index[3 * (size_t)b + d] + (code[d] < 0 ? -1 : (code[d] > 0 ? 2 : bit));
+        }
+        if (used) row[icode * 8 + q] = mo->leaf(l + 1, fi);
+      }
+    }
+  }
+  if (finer.empty()) finer.assign(216, -1);
+}
+
 static int grad_chi_run(const Grid *mo, int64_t nloc, const double *chi, double *tmpV, double Rtol, double Ctol, int level_max_vorticity) {
   std::vector<int32_t> finer_row, finer;
   try {
-    finer_row.assign((size_t)nloc, -1);
-    for (int64_t b = 0; b < nloc; ++b) {
-      bool any = false;
-      for (int c = 0; c < 27; ++c) any = any || mo->nbr27[27 * (size_t)b + c] == kNbrFiner;
-      if (!any) continue;
-      finer_row[b] = (int32_t)(finer.size() / 216);
-      finer.resize(finer.size() + 216, -1);
-      int32_t *row = finer.data() + finer.size() - 216;
-      const int l = mo->blevel[b];
-      for (int icode = 0; icode < 27; ++icode) {
-        if (mo->nbr27[27 * (size_t)b + icode] != kNbrFiner) continue;
-        const int code[3] = {icode % 3 - 1, (icode / 3) % 3 - 1, icode / 9 - 1};
-        for (int q = 0; q < 8; ++q) {
-          int fi[3];
-          bool used = true;
-          for (int d = 0; d < 3; ++d) {
-            const int bit = (q >> d) & 1;
-            if (code[d] != 0 && bit) used = false;
-            fi[d] = 2 * mo->index[3 * (size_t)b + d] + (code[d] < 0 ? -1 : (code[d] > 0 ? 2 : bit));
-          }
-          if (used) row[icode * 8 + q] = mo->leaf(l + 1, fi);
-        }
-      }
-    }
+    finer_tables(mo, nloc, finer_row, finer);
   } catch (const std::exception &e) {
     set_error("cup3d_grad_chi_on_tmp: %s", e.what());
     return CUP3D_EINVAL;
   }
-  if (finer.empty()) finer.assign(216, -1);
   DevInts d_row, d_finer, d_n27, d_nbr, d_index, d_level;
   int rc;
   if ((rc = d_row.upload(finer_row)) || (rc = d_finer.upload(finer)) || (rc = d_n27.upload(mo->nbr27)) || (rc = d_nbr.upload(mo->nbr)) ||
@@ -1011,3 +1019,342 @@ extern "C" int cup3d_debug_amr_slabs(cup3d_sim_t *h, int field, int w, double *o
   return CUP3D_OK;
 }
 #endif
+
+// ==== cup3d_sim_labs / cup3d_sim_labs_device.  Ghosted block tiles of any stencil box on demand: BlockLab::load + post_load (main.cpp:3623-3787) for a list of blocks.
+// It lives in this file because it uses the device helpers above -- avg_down8 / avg_block, fd_mode_av / fd_mode_blend (with interp1d),
+// test_interp -- and the finer-leaf tables of k_grad_chi, none of them restated.
+//
+// The stencil kernels build the three tile shapes they need in LDS and never hand them out; this is the general operation for a
+// consumer OUTSIDE the library (the kernel-functor protocol of compute<Lab>): block b with its ghosts for the box [-w, w+1)^3,
+// w = 1..4, star or tensorial, in the reference's Matrix3D layout [L][L][L][nc] (x fastest, component innermost, L = 8 + 2w).
+// One workgroup per tile, one component at a time in LDS (16^3 fine cells + the 10^3 coarse shadow tile = 40 768 B), in the
+// reference's order:
+//   A. interior copy, SameLevelExchange (3823-3876), FineToCoarseExchange = AverageDown of the finer leaves (3907-4065);
+//   B. the coarse shadow tile m_CoarsenedBlock: coarser leaves copied (CoarseFineExchange 4066-4170), same-level neighbours
+//      averaged down (FillCoarseVersion 4171-4235; every one of them -- the cells the UseCoarseStencil rule 3788-3822 would leave
+//      out are read by no interpolation: tests/test_gpu_labs.py::test_tiles_equal_the_reference, the reference's own tiles on four
+//      meshes, is the test that a violation would turn red), the block's own average-down (post_load 3750-3778);
+//   C. _apply_bc on the coarse tile (3781): ordered passes x, y, z, each over the whole ghost slab;
+//   D. CoarseFineInterpolation (4236-4614): TestInterp everywhere behind a coarser neighbour, then the finite-difference mode with
+//      the 1/15 blend on the two layers next to a FACE (it overwrites TestInterp there, as in the reference);
+//   E. _apply_bc on the fine tile: ordered passes x, y, z, each over the whole ghost slab, transverse ghosts of earlier passes included;
+//   F. the cells the reference leaves undefined -- edge and corner ghosts of a star tile with w <= 2, where use_averages (3618-3621)
+//      does not hold -- leave as quiet NaN, so that a consumer that reads them sees it.
+// A tile with w >= 3 is built tensorially by the reference whatever the stencil says (use_averages), so `tensorial` only decides F.
+// The kernel reads blocks only: it neither needs nor touches the ghost slabs the stencil kernels keep behind kNbrHalo.
+namespace cup3d {
+
+struct LabDev {
+  const int32_t *n27;        // [nb][27]
+  const int32_t *index;      // [nb][3]
+  const int32_t *level;      // [nb]
+  const int32_t *finer_row;  // [nb]: row of `finer`, or -1
+  const int32_t *finer;      // [rows][27][8]
+  int bpd[3], bc[3];
+  int bc_comp;  // scalar fields: -1 = zero-gradient domain faces (ScalarLab); k = element of BlockLabBC<.., direction k>
+};
+
+constexpr int kLabCoarse = 10;  // coarse shadow tile: coarse cells [-3, 7)^3 (w = 4 reads [-3, 6])
+__device__ __forceinline__ int cix10(int X, int Y, int Z) { return ((Z + 3) * kLabCoarse + (Y + 3)) * kLabCoarse + (X + 3); }
+
+// domain-face rule of one tile value: the vector lab negates every component at a wall and the normal one at a freespace face
+// (6107-6503), the scalar lab copies (6561-6581), the scalar of BlockLabBC<.., direction k> behaves as component k of a vector
+__device__ __forceinline__ double lab_bc_value(double v, int nc, int c, int bc_comp, int bc_kind, int d) {
+  const int cc = nc == 3 ? c : bc_comp;
+  return (cc >= 0 && (bc_kind == CUP3D_BC_WALL || cc == d)) ? -v : v;
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) k_labs(LabDev a, const int32_t *__restrict__ slots, int first, int star, const double *__restrict__ src, int nc,
+                                              double *__restrict__ out) {
+  constexpr int L = 8 + 2 * W, L3 = L * L * L, C3 = kLabCoarse * kLabCoarse * kLabCoarse;
+  __shared__ double lab[L3];
+  __shared__ double Ct[C3];
+  const int t = threadIdx.x;
+  const int pb = slots ? slots[blockIdx.x] : first + (int)blockIdx.x;
+  double *__restrict__ tile = out + (size_t)blockIdx.x * L3 * nc;
+  const int32_t *n27 = a.n27 + 27 * (size_t)pb;
+  const int32_t *fin = a.finer_row[pb] >= 0 ? a.finer + (size_t)a.finer_row[pb] * 216 : nullptr;
+  const int idx[3] = {a.index[3 * pb], a.index[3 * pb + 1], a.index[3 * pb + 2]};
+  const int par[3] = {idx[0] & 1, idx[1] & 1, idx[2] & 1};
+  const int lev = a.level[pb];
+  bool has_coarse = false;
+  for (int i = 0; i < 27; ++i) has_coarse = has_coarse || n27[i] >= kNbrCoarser;
+  // domain faces of this block: bit f of `dom` (f = x-, x+, y-, y+, z-, z+) where a boundary condition sits behind the face
+  int dom = 0;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    if (a.bc[d] == CUP3D_BC_PERIODIC) continue;
+    if (idx[d] == 0) dom |= 1 << (2 * d);
+    if (idx[d] == (a.bpd[d] << lev) - 1) dom |= 2 << (2 * d);
+  }
+  auto lix = [](int x, int y, int z) { return ((z + W) * L + (y + W)) * L + (x + W); };
+  for (int c = 0; c < nc; ++c) {
+    const double *__restrict__ own = src + ((size_t)pb * nc + c) * 512;
+    // A. centre, same-level neighbours, finer neighbours (averaged down)
+    for (int e = t; e < L3; e += 256) {
+      const int l[3] = {e % L - W, (e / L) % L - W, e / (L * L) - W};
+      int code[3], loc[3], fl[3], q = 0;
+      for (int d = 0; d < 3; ++d) {
+        code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
+        loc[d] = l[d] - 8 * code[d];
+        fl[d] = code[d] < 0 ? 8 + 2 * l[d] : (code[d] > 0 ? 2 * (l[d] - 8) : (2 * l[d]) & 7);
+        if (code[d] == 0 && l[d] >= 4) q |= 1 << d;
+      }
+      const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
+      const int n = n27[icode];
+      double v = 0.0;
+      if (n >= 0 && n < kNbrCoarser) v = src[((size_t)n * nc + c) * 512 + (loc[2] * 8 + loc[1]) * 8 + loc[0]];
+      else if (n == kNbrFiner && fin && fin[icode * 8 + q] >= 0) v = avg_block(src + ((size_t)fin[icode * 8 + q] * nc + c) * 512, fl[0], fl[1], fl[2]);
+      lab[e] = v;
+    }
+    __syncthreads();
+    if (has_coarse) {
+      // B. coarse shadow tile
+      for (int e = t; e < C3; e += 256) {
+        const int P[3] = {e % kLabCoarse - 3, (e / kLabCoarse) % kLabCoarse - 3, e / (kLabCoarse * kLabCoarse) - 3};
+        int code[3];
+        for (int d = 0; d < 3; ++d) code[d] = P[d] < 0 ? -1 : (P[d] > 3 ? 1 : 0);
+        const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
+        const int n = n27[icode];
+        double v = 0.0;
+        if (icode == 13) {
+          double w[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) w[q] = own[((2 * P[2] + (q >> 2)) * 8 + 2 * P[1] + ((q >> 1) & 1)) * 8 + 2 * P[0] + (q & 1)];  // x fastest here
+          v = avg_down8(w);
+        } else if (n >= kNbrCoarser) {
+          v = src[((size_t)(n - kNbrCoarser) * nc + c) * 512 + ((par[2] * 4 + P[2] + 8) & 7) * 64 + ((par[1] * 4 + P[1] + 8) & 7) * 8 + ((par[0] * 4 + P[0] + 8) & 7)];
+        } else if (n >= 0) {
+          v = avg_block(src + ((size_t)n * nc + c) * 512, 2 * P[0] - 8 * code[0], 2 * P[1] - 8 * code[1], 2 * P[2] - 8 * code[2]);
+        }
+        Ct[e] = v;
+      }
+      __syncthreads();
+      // C. domain faces on the coarse tile: the three ghost layers behind the face, every transverse position, from the face cell.
+      //    One pass per axis does both sides: each writes ghosts of its own side and reads the face cells, which no pass writes
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        if (!((dom >> (2 * d)) & 3)) continue;
+        constexpr int per_side = 3 * kLabCoarse * kLabCoarse;
+        const int d1 = (d + 1) % 3, d2 = (d + 2) % 3;
+        for (int i = t; i < 2 * per_side; i += 256) {
+          const int side = i / per_side, j = i - side * per_side;
+          if (!((dom >> (2 * d + side)) & 1)) continue;
+          const int layer = j / (kLabCoarse * kLabCoarse), r = j - layer * (kLabCoarse * kLabCoarse);
+          int p[3], q[3];
+          p[d] = side ? 4 + layer : -1 - layer;
+          q[d] = side ? 3 : 0;
+          p[d1] = q[d1] = r % kLabCoarse - 3;
+          p[d2] = q[d2] = r / kLabCoarse - 3;
+          Ct[cix10(p[0], p[1], p[2])] = lab_bc_value(Ct[cix10(q[0], q[1], q[2])], nc, c, a.bc_comp, a.bc[d], d);
+        }
+        __syncthreads();
+      }
+      // D. ghosts behind coarser neighbours
+      for (int e = t; e < L3; e += 256) {
+        const int l[3] = {e % L - W, (e / L) % L - W, e / (L * L) - W};
+        int code[3], X[3], bit[3], ncode = 0;
+        for (int d = 0; d < 3; ++d) {
+          code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
+          ncode += code[d] != 0;
+          X[d] = l[d] >> 1;   // the coarse cell that holds this fine cell
+          bit[d] = l[d] & 1;  // which of its two children along d
+        }
+        if (ncode == 0 || n27[(code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1)] < kNbrCoarser) continue;
+        const int ax = code[0] ? 0 : (code[1] ? 1 : 2);
+        const int layer = code[ax] < 0 ? -1 - l[ax] : l[ax] - 8;
+        double v;
+        if (ncode == 1 && layer < 2) {  // the two layers next to a face: finite-difference mode
+          const int ax1 = ax == 0 ? 1 : 0, ax2 = ax == 2 ? 1 : 2;
+          const int st1 = ax1 == 0 ? 1 : kLabCoarse, st2 = ax2 == 1 ? kLabCoarse : kLabCoarse * kLabCoarse;
+          const double av = fd_mode_av(Ct + cix10(X[0], X[1], X[2]), X[ax1], X[ax2], st1, st2, bit[ax1], bit[ax2]);
+          int cb[3] = {l[0], l[1], l[2]}, cc[3] = {l[0], l[1], l[2]};
+          cb[ax] = code[ax] > 0 ? 7 : 0;
+          cc[ax] = code[ax] > 0 ? 6 : 1;
+          v = fd_mode_blend(av, lab[lix(cb[0], cb[1], cb[2])], lab[lix(cc[0], cc[1], cc[2])], layer);
+        } else {  // deeper layers, edges and corners: TestInterp
+          v = test_interp([&](int i, int j, int k) -> double { return Ct[cix10(X[0] - 1 + i, X[1] - 1 + j, X[2] - 1 + k)]; }, bit);
+        }
+        lab[e] = v;
+      }
+      __syncthreads();
+    }
+    // E. domain faces on the fine tile: the W ghost layers behind the face, every transverse position (the ghosts earlier passes wrote
+    //    included), from the face cell; one pass per axis, both sides, as on the coarse tile
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      if (!((dom >> (2 * d)) & 3)) continue;
+      constexpr int per_side = W * L * L;
+      const int d1 = (d + 1) % 3, d2 = (d + 2) % 3;
+      for (int i = t; i < 2 * per_side; i += 256) {
+        const int side = i / per_side, j = i - side * per_side;
+        if (!((dom >> (2 * d + side)) & 1)) continue;
+        const int layer = j / (L * L), r = j - layer * (L * L);
+        int p[3], q[3];
+        p[d] = side ? 8 + layer : -1 - layer;
+        q[d] = side ? 7 : 0;
+        p[d1] = q[d1] = r % L - W;
+        p[d2] = q[d2] = r / L - W;
+        lab[lix(p[0], p[1], p[2])] = lab_bc_value(lab[lix(q[0], q[1], q[2])], nc, c, a.bc_comp, a.bc[d], d);
+      }
+      __syncthreads();
+    }
+    // F. the tile leaves in the reference's layout; what the reference leaves undefined leaves as NaN
+    for (int e = t; e < L3; e += 256) {
+      double v = lab[e];
+      if (W <= 2 && star) {
+        const int x = e % L - W, y = (e / L) % L - W, z = e / (L * L) - W;
+        if ((x < 0 || x > 7) + (y < 0 || y > 7) + (z < 0 || z > 7) > 1) v = __builtin_nan("");
+      }
+      tile[(size_t)e * nc + c] = v;
+    }
+    __syncthreads();
+  }
+}
+
+// ---- host side
+constexpr size_t kLabStageBytes = (size_t)64 << 20;  // device staging buffer of the host variant
+constexpr long kLabSlotCap = 8192;                   // listed tiles per launch (the smallest tile, 10^3 doubles, fills the buffer with as many)
+
+struct LabTables {
+  int32_t *n27 = nullptr, *index = nullptr, *level = nullptr, *finer_row = nullptr, *finer = nullptr;
+  int32_t *d_slots = nullptr, *h_slots = nullptr;  // slot list of one launch: device copy, pinned host copy
+  hipEvent_t ev_slots = nullptr;                   // the upload that last read h_slots
+  bool slots_in_flight = false;
+  double *stage = nullptr;
+};
+
+void labs_destroy(Sim *s) {
+  LabTables *T = s->labs;
+  if (!T) return;
+  void *dev[] = {T->n27, T->index, T->level, T->finer_row, T->finer, T->d_slots, T->stage};
+  for (void *p : dev) if (p) (void)hipFree(p);
+  if (T->h_slots) (void)hipHostFree(T->h_slots);
+  if (T->ev_slots) (void)hipEventDestroy(T->ev_slots);
+  delete T;
+  s->labs = nullptr;
+}
+
+// tables of k_labs, built when the first tile is asked for: a uniform grid is read as the one-level mesh it is (Grid::as_mesh)
+static int labs_prepare(Sim *s, bool want_stage) {
+  if (!s->labs) {
+    std::unique_ptr<Grid> tmp;
+    const Grid *mo = s->grid;
+    std::vector<int32_t> finer_row, finer;
+    try {
+      if (!mo->multilevel) { tmp = mo->as_mesh(); mo = tmp.get(); }
+      finer_tables(mo, mo->nblocks(), finer_row, finer);
+    } catch (const std::exception &e) {
+      set_error("cup3d_sim_labs: %s", e.what());
+      return CUP3D_EINVAL;
+    }
+    s->labs = new LabTables();
+    LabTables *T = s->labs;
+    auto up = [&](int32_t **d, const std::vector<int32_t> &v) -> int {
+      CUP3D_HIP(hipMalloc((void **)d, std::max<size_t>(v.size(), 1) * sizeof(int32_t)));
+      if (!v.empty()) CUP3D_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      s->bytes += v.size() * sizeof(int32_t);
+      return CUP3D_OK;
+    };
+    int rc;
+    if ((rc = up(&T->n27, mo->nbr27)) || (rc = up(&T->index, mo->index)) || (rc = up(&T->level, mo->blevel)) || (rc = up(&T->finer_row, finer_row)) ||
+        (rc = up(&T->finer, finer))) {
+      labs_destroy(s);
+      return rc;
+    }
+    hipError_t e = hipMalloc((void **)&T->d_slots, kLabSlotCap * sizeof(int32_t));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&T->h_slots, kLabSlotCap * sizeof(int32_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&T->ev_slots, hipEventDisableTiming);
+    if (e != hipSuccess) {
+      labs_destroy(s);
+      return hip_fail(e, "labs_prepare", __FILE__, __LINE__);
+    }
+    s->bytes += kLabSlotCap * sizeof(int32_t);
+  }
+  if (want_stage && !s->labs->stage) {
+    CUP3D_HIP(hipMalloc((void **)&s->labs->stage, kLabStageBytes));
+    s->bytes += kLabStageBytes;
+  }
+  return CUP3D_OK;
+}
+
+// tiles [t0, t0 + m) of the request -> out (device), on the compute stream; m <= kLabSlotCap when slots are listed
+static int labs_launch(Sim *s, const double *f, int nc, long t0, long m, const int32_t *slots, int w, int tensorial, int bc_comp, double *out) {
+  LabTables *T = s->labs;
+  const Grid *g = s->grid;
+  LabDev a{T->n27, T->index, T->level, T->finer_row, T->finer, {g->bpd[0], g->bpd[1], g->bpd[2]}, {g->bc[0], g->bc[1], g->bc[2]}, nc == 1 ? bc_comp : -1};
+  const int32_t *d_slots = nullptr;
+  if (slots) {
+    if (T->slots_in_flight) CUP3D_HIP(hipEventSynchronize(T->ev_slots));  // the pinned copy is free again
+    memcpy(T->h_slots, slots + t0, (size_t)m * sizeof(int32_t));
+    CUP3D_HIP(hipMemcpyAsync(T->d_slots, T->h_slots, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, stream()));
+    CUP3D_HIP(hipEventRecord(T->ev_slots, stream()));
+    T->slots_in_flight = true;
+    d_slots = T->d_slots;
+  }
+  const int star = tensorial ? 0 : 1;
+  ProfileScope ps("labs");
+  switch (w) {
+    case 1: hipLaunchKernelGGL(k_labs<1>, dim3((unsigned)m), dim3(256), 0, stream(), a, d_slots, (int)t0, star, f, nc, out); break;
+    case 2: hipLaunchKernelGGL(k_labs<2>, dim3((unsigned)m), dim3(256), 0, stream(), a, d_slots, (int)t0, star, f, nc, out); break;
+    case 3: hipLaunchKernelGGL(k_labs<3>, dim3((unsigned)m), dim3(256), 0, stream(), a, d_slots, (int)t0, star, f, nc, out); break;
+    default: hipLaunchKernelGGL(k_labs<4>, dim3((unsigned)m), dim3(256), 0, stream(), a, d_slots, (int)t0, star, f, nc, out); break;
+  }
+  CUP3D_HIP(hipGetLastError());
+  return CUP3D_OK;
+}
+
+// the checks both entry points share; nothing is allocated or launched before they pass
+static int labs_check(Sim *s, int field, long n, const int32_t *slots, int width, int scalar_dir, const void *out, const double **f, int *nc) {
+  if (!out) { set_error("cup3d_sim_labs: null output"); return CUP3D_EINVAL; }
+  *f = s->field(field, nc);
+  if (!*f) { set_error("unknown field id %d", field); return CUP3D_EINVAL; }
+  if (width < 1 || width > 4) { set_error("cup3d_sim_labs: width %d; the tiles are pinned for the boxes [-w, w+1), w = 1..4", width); return CUP3D_EINVAL; }
+  if (scalar_dir < -1 || scalar_dir > 2) { set_error("cup3d_sim_labs: scalar_dir %d (expected -1, 0, 1 or 2)", scalar_dir); return CUP3D_EINVAL; }
+  if (scalar_dir >= 0 && *nc == 3) { set_error("cup3d_sim_labs: scalar_dir %d on a vector field (it selects BlockLabBC<.., direction> for a scalar)", scalar_dir); return CUP3D_EINVAL; }
+  if (s->grid->n_local >= 0 || s->grid->nranks > 1) {
+    set_error("cup3d_sim_labs: this sim holds one rank's share of a grid spread over %d ranks; tiles whose neighbours live on another rank are out of scope "
+              "(they need the tensorial ghost-block exchange at stencil width)", s->grid->nranks);
+    return CUP3D_EINVAL;
+  }
+  if (n < 0 || (!slots && n != (long)s->nb)) { set_error("cup3d_sim_labs: n = %ld (slots = NULL asks for all %ld local blocks)", n, (long)s->nb); return CUP3D_EINVAL; }
+  if (slots)
+    for (long i = 0; i < n; ++i)
+      if (slots[i] < 0 || slots[i] >= s->nb) { set_error("block slot %d out of range", (int)slots[i]); return CUP3D_EINVAL; }
+  return CUP3D_OK;
+}
+
+}  // namespace cup3d
+
+extern "C" int cup3d_sim_labs_device(cup3d_sim_t *h, int field, long n, const int32_t *slots, int width, int tensorial, int scalar_dir, void *device_out) {
+  if (!h) return CUP3D_EINVAL;
+  Sim *s = reinterpret_cast<Sim *>(h);
+  const double *f;
+  int nc, rc;
+  if ((rc = labs_check(s, field, n, slots, width, scalar_dir, device_out, &f, &nc)) || (rc = labs_prepare(s, false))) return rc;
+  const size_t L = 8 + 2 * (size_t)width, per = L * L * L * nc;
+  for (long t0 = 0; t0 < n; t0 += kLabSlotCap) {
+    const long m = std::min(kLabSlotCap, n - t0);
+    if ((rc = labs_launch(s, f, nc, t0, m, slots, width, tensorial, scalar_dir, (double *)device_out + (size_t)t0 * per))) return rc;
+  }
+  return CUP3D_OK;
+}
+
+extern "C" int cup3d_sim_labs(cup3d_sim_t *h, int field, long n, const int32_t *slots, int width, int tensorial, int scalar_dir, double *host_out) {
+  if (!h) return CUP3D_EINVAL;
+  Sim *s = reinterpret_cast<Sim *>(h);
+  const double *f;
+  int nc, rc;
+  if ((rc = labs_check(s, field, n, slots, width, scalar_dir, host_out, &f, &nc)) || (rc = labs_prepare(s, true))) return rc;
+  const size_t L = 8 + 2 * (size_t)width, per = L * L * L * nc;
+  const long cap = std::max<long>(1, std::min<long>(kLabSlotCap, (long)(kLabStageBytes / (per * sizeof(double)))));
+  for (long t0 = 0; t0 < n; t0 += cap) {  // the staging buffer is bounded: large requests go through it chunk by chunk
+    const long m = std::min(cap, n - t0);
+    if ((rc = labs_launch(s, f, nc, t0, m, slots, width, tensorial, scalar_dir, s->labs->stage))) return rc;
+    CUP3D_HIP(hipMemcpyAsync(host_out + (size_t)t0 * per, s->labs->stage, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+  }
+  stats_field_download((size_t)n * per * sizeof(double));
+  return CUP3D_OK;
+}

@@ -92,6 +92,7 @@ int not_in_release(const char *what) {
 // ---- cup3d_stats_*: process-wide counters (the ranks of the in-process test communicator are threads, hence atomics)
 static std::atomic<long> g_st_halo{0}, g_st_halo_bytes{0}, g_st_allreduce{0}, g_st_waits{0}, g_st_wait_ns{0}, g_st_iters{0}, g_st_h2d{0}, g_st_d2h{0};
 static void stats_field_transfer(bool up, size_t bytes) { (up ? g_st_h2d : g_st_d2h) += (long)bytes; }
+void stats_field_download(size_t bytes) { stats_field_transfer(false, bytes); }
 void stats_host_wait(double seconds) { g_st_waits++; g_st_wait_ns += (long)(seconds * 1e9); }
 void stats_solver_iterations(long n) { g_st_iters += n; }
 void stats_halo(size_t bytes_sent) { g_st_halo++; g_st_halo_bytes += (long)bytes_sent; }
@@ -530,6 +531,7 @@ void cup3d_sim_destroy(cup3d_sim_t *h) {
   vcomm_unregister(s);
   hipStreamSynchronize(g_stream);
   mg_destroy(s);
+  labs_destroy(s);
   double *ptrs[] = {s->vel, s->vel2, s->tmpV, s->pres, s->lhs, s->chi, s->pold, s->d_partials, s->d_red, s->halo_recv, s->halo_send, s->d_block_dots,
                     s->d_hb, s->d_flux};
   for (double *p : ptrs) if (p) hipFree(p);

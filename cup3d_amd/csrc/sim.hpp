@@ -58,6 +58,7 @@ void stats_host_wait(double seconds);
 void stats_solver_iterations(long n);
 void stats_halo(size_t bytes_sent);
 void stats_allreduce();
+void stats_field_download(size_t bytes);  // field data handed to the host outside cup3d_sim_download* (cup3d_sim_labs)
 
 struct Comm;  // RCCL state (comm.cpp)
 Comm *comm();  // nullptr when single rank
@@ -135,6 +136,7 @@ struct Sim {
   struct LoopSums *d_loop_sums = nullptr;  // [2] (poisson.hip)
   unsigned *h_early_fail = nullptr, *h_early_fail_dev = nullptr;  // pinned: a bounded device-side wait of the early all-reduce gave up
   void *mg = nullptr;              // level hierarchy of the multigrid preconditioner (multigrid.hip), built on first use
+  struct LabTables *labs = nullptr;  // tables and staging buffer of cup3d_sim_labs (amr.hip), built on first use
   int max_groups = 0;
   // staging for host transfers
   double *d_stage = nullptr;
@@ -224,6 +226,7 @@ int launch_mean_total(Sim *s);  // total of the block sums in d_partials' tail -
 // block_solver 5: one multigrid V-cycle from a zero guess as M^-1 (multigrid.hip; an alternative, not the reference's algorithm)
 int mg_vcycle(Sim *s, const double *in, double *out);
 void mg_destroy(Sim *s);
+void labs_destroy(Sim *s);  // what cup3d_sim_labs built on first use (amr.hip)
 // implicit diffusion (DiffusionSolver, main.cpp:6719-7147): Helmholtz operator of velocity component `direction`
 struct HelmholtzOp { int direction; double dt, nu; };
 int launch_lhs_diffusion(Sim *s, const double *p, double *out, const HelmholtzOp &op);

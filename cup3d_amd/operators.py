@@ -273,6 +273,35 @@ class SimulationData:
         check(lib().cup3d_sim_download_block_list(self.handle, fid, len(sl), sl.ctypes.data_as(C.c_void_p), self._block_ptrs(out)))
         return out
 
+    def _labs_args(self, field, width, slots):
+        fid = FIELDS[field]
+        sl = None if slots is None else np.ascontiguousarray(slots, dtype=np.int32)
+        n = self.nblocks if sl is None else len(sl)
+        L = 8 + 2 * int(width)
+        shape = (n, L, L, L, 3) if FIELD_NCOMP[fid] == 3 else (n, L, L, L)
+        return fid, sl, n, shape
+
+    def labs(self, field, width, tensorial=False, slots=None, scalar_dir=-1):
+        """Ghosted tiles of the listed blocks (all of them, in slot order, when slots is None) for the stencil box
+        [-width, width+1), width 1..4, star or tensorial: BlockLab::load + post_load (main.cpp:3623-3787) on the device
+        (cup3d_sim_labs).  ndarray [n, L, L, L, nc], L = 8 + 2*width, z, y, x order (nc dropped for scalars, as download does);
+        the edge and corner ghosts of a star tile with width <= 2 are NaN.  scalar_dir 0..2: a scalar field's tile as
+        BlockLabBC<.., direction> (implicit diffusion).  Only the tiles cross the host boundary, not the field."""
+        fid, sl, n, shape = self._labs_args(field, width, slots)
+        out = np.empty(shape)
+        check(lib().cup3d_sim_labs(self.handle, fid, n, None if sl is None else sl.ctypes.data_as(C.c_void_p), int(width), int(bool(tensorial)),
+                                   int(scalar_dir), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def labs_into(self, ptr, field, width, tensorial=False, slots=None, scalar_dir=-1):
+        """The same into device memory at `ptr` (e.g. torch.empty(shape, dtype=torch.float64, device="cuda").data_ptr()), which
+        must hold n*L^3*nc doubles: stream-ordered on the library's compute stream, no synchronisation (cup3d_sim_labs_device).
+        Returns the shape of the tiles written."""
+        fid, sl, n, shape = self._labs_args(field, width, slots)
+        check(lib().cup3d_sim_labs_device(self.handle, fid, n, None if sl is None else sl.ctypes.data_as(C.c_void_p), int(width),
+                                          int(bool(tensorial)), int(scalar_dir), C.c_void_p(int(ptr))))
+        return shape
+
     def _like(self, **kw):
         """A SimulationData with this one's run parameters on another mesh (leaves=... or view=...), run state carried along."""
         new = SimulationData(bpdx=self.bpdx, bpdy=self.bpdy, bpdz=self.bpdz, levelMax=self.levelMax, levelStart=self.levelStart,

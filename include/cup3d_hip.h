@@ -184,6 +184,22 @@ CUP3D_API int cup3d_sim_download_blocks(cup3d_sim_t *, int field, void *const *b
  * without a full-field round trip */
 CUP3D_API int cup3d_sim_upload_block_list(cup3d_sim_t *, int field, long n, const int32_t *slots, const void *const *block_ptrs);
 CUP3D_API int cup3d_sim_download_block_list(cup3d_sim_t *, int field, long n, const int32_t *slots, void *const *block_ptrs);
+/* BlockLab::load + post_load (main.cpp:3623-3787) for the listed blocks: tiles [n][L][L][L][nc], L = 8 + 2*width,
+ * box [-width, width+1), width 1..4; slots = NULL: all local blocks in slot order.
+ * scalar_dir: -1 = the field's own lab (VectorLab for vel/tmpV, ScalarLab for scalar fields);
+ *             0..2 = scalar field as BlockLabBC<.., direction> (implicit diffusion).
+ * The tile is the reference's Matrix3D: x fastest, component innermost; same-level ghosts copied, finer neighbours averaged down,
+ * coarser ones interpolated (TestInterp / the finite-difference mode), domain faces last, bit for bit.  tensorial = 0 with width <= 2
+ * is the star tile: its edge and corner ghosts, which the reference leaves undefined, are quiet NaN.  What lets a host functor that
+ * needs the [s,e) tiles of a few blocks (ComputeForces reads [-4,5) around an obstacle, 12250-12503) get them without downloading
+ * a field: 98 304 B per [-4,5) vector tile.  Repeated and unordered slots are allowed.  Both variants launch the same kernel on the
+ * compute stream (cup3d_set_stream); the host variant stages through a bounded device buffer of the sim, counts its bytes in
+ * cup3d_run_stats.field_bytes_downloaded and synchronises before it returns; the device variant is stream-ordered and does not.
+ * CUP3D_EINVAL, nothing touched: width outside 1..4, unknown field, NULL output, slot outside [0, nblocks), n != nblocks with
+ * slots = NULL, scalar_dir >= 0 on a vector field, a sim on a rank view or on one rank's share of a uniform grid (tiles whose
+ * neighbours live on another rank are out of scope). */
+CUP3D_API int cup3d_sim_labs(cup3d_sim_t *, int field, long n, const int32_t *slots, int width, int tensorial, int scalar_dir, double *host_out);
+CUP3D_API int cup3d_sim_labs_device(cup3d_sim_t *, int field, long n, const int32_t *slots, int width, int tensorial, int scalar_dir, void *device_out);
 CUP3D_API int cup3d_sim_upload(cup3d_sim_t *, int field, const double *blocks);
 CUP3D_API int cup3d_sim_download(cup3d_sim_t *, int field, double *blocks);
 CUP3D_API int cup3d_sim_fill(cup3d_sim_t *, int field, double value);

@@ -136,6 +136,8 @@ SIGNATURES = {
     "cup3d_sim_download_block_list": (C.c_int, [_vp, C.c_int, C.c_long, _vp, _vp]),
     "cup3d_sim_labs": (C.c_int, [_vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "cup3d_sim_labs_device": (C.c_int, [_vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "cup3d_sim_labs_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "cup3d_sim_labs_over_ranks_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "cup3d_advect_diffuse_implicit": (C.c_int, [_vp, C.c_double, C.c_double, _dp, C.POINTER(PoissonParams), C.POINTER(PoissonResult)]),
     "cup3d_advect_implicit": (C.c_int, [_vp, C.c_double, C.c_double, _dp]),
     "cup3d_diffusion_rhs": (C.c_int, [_vp]),

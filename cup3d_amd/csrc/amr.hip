@@ -15,6 +15,7 @@
 //     down (FillCoarseVersion 4171-4235), domain faces mirrored (_apply_bc on the coarse tile, 3781).
 // After the kernel, k_flux_fix applies FluxCorrectionMPI::FillBlockCases (2825-2935) to the coarse side.
 // All arithmetic keeps the reference's association (-ffp-contract=off): results are bit-identical to it.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -1064,153 +1065,39 @@ __device__ __forceinline__ double lab_bc_value(double v, int nc, int c, int bc_c
   return (cc >= 0 && (bc_kind == CUP3D_BC_WALL || cc == d)) ? -v : v;
 }
 
+// Phases A-F live once, in labs_body.hpp, and are included into the two kernels below, which differ in where the blocks of a tile's
+// neighbourhood live.  k_labs, one rank: every slot is a row of the field array.  k_labs_view, a mesh spread over ranks
+// (cup3d_sim_labs_over_ranks): slots [0, n_local) of the rank's tensorial view are rows of the sim's own field array, read in place; a
+// ghost slot is a row of the call's ghost pool, found through pool_of (-1: not fetched -- row 0 of the pool, which holds NaN, so that
+// a read the request plan did not foresee shows in the tile instead of leaving the buffer).
+struct LabSrcView {
+  const double *__restrict__ field;
+  const double *__restrict__ pool;      // [1 + fetched ghosts][nc][512]
+  const int32_t *__restrict__ pool_of;  // [nghost]
+  int n_local;
+  __device__ __forceinline__ const double *blk(int slot, int nc, int c) const {
+    if (slot < n_local) return field + ((size_t)slot * nc + c) * 512;
+    return pool + ((size_t)(pool_of[slot - n_local] + 1) * nc + c) * 512;
+  }
+};
+
 template <int W>
 __global__ void __launch_bounds__(256) k_labs(LabDev a, const int32_t *__restrict__ slots, int first, int star, const double *__restrict__ src, int nc,
                                               double *__restrict__ out) {
-  constexpr int L = 8 + 2 * W, L3 = L * L * L, C3 = kLabCoarse * kLabCoarse * kLabCoarse;
-  __shared__ double lab[L3];
-  __shared__ double Ct[C3];
-  const int t = threadIdx.x;
-  const int pb = slots ? slots[blockIdx.x] : first + (int)blockIdx.x;
-  double *__restrict__ tile = out + (size_t)blockIdx.x * L3 * nc;
-  const int32_t *n27 = a.n27 + 27 * (size_t)pb;
-  const int32_t *fin = a.finer_row[pb] >= 0 ? a.finer + (size_t)a.finer_row[pb] * 216 : nullptr;
-  const int idx[3] = {a.index[3 * pb], a.index[3 * pb + 1], a.index[3 * pb + 2]};
-  const int par[3] = {idx[0] & 1, idx[1] & 1, idx[2] & 1};
-  const int lev = a.level[pb];
-  bool has_coarse = false;
-  for (int i = 0; i < 27; ++i) has_coarse = has_coarse || n27[i] >= kNbrCoarser;
-  // domain faces of this block: bit f of `dom` (f = x-, x+, y-, y+, z-, z+) where a boundary condition sits behind the face
-  int dom = 0;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    if (a.bc[d] == CUP3D_BC_PERIODIC) continue;
-    if (idx[d] == 0) dom |= 1 << (2 * d);
-    if (idx[d] == (a.bpd[d] << lev) - 1) dom |= 2 << (2 * d);
-  }
-  auto lix = [](int x, int y, int z) { return ((z + W) * L + (y + W)) * L + (x + W); };
-  for (int c = 0; c < nc; ++c) {
-    const double *__restrict__ own = src + ((size_t)pb * nc + c) * 512;
-    // A. centre, same-level neighbours, finer neighbours (averaged down)
-    for (int e = t; e < L3; e += 256) {
-      const int l[3] = {e % L - W, (e / L) % L - W, e / (L * L) - W};
-      int code[3], loc[3], fl[3], q = 0;
-      for (int d = 0; d < 3; ++d) {
-        code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
-        loc[d] = l[d] - 8 * code[d];
-        fl[d] = code[d] < 0 ? 8 + 2 * l[d] : (code[d] > 0 ? 2 * (l[d] - 8) : (2 * l[d]) & 7);
-        if (code[d] == 0 && l[d] >= 4) q |= 1 << d;
-      }
-      const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
-      const int n = n27[icode];
-      double v = 0.0;
-      if (n >= 0 && n < kNbrCoarser) v = src[((size_t)n * nc + c) * 512 + (loc[2] * 8 + loc[1]) * 8 + loc[0]];
-      else if (n == kNbrFiner && fin && fin[icode * 8 + q] >= 0) v = avg_block(src + ((size_t)fin[icode * 8 + q] * nc + c) * 512, fl[0], fl[1], fl[2]);
-      lab[e] = v;
-    }
-    __syncthreads();
-    if (has_coarse) {
-      // B. coarse shadow tile
-      for (int e = t; e < C3; e += 256) {
-        const int P[3] = {e % kLabCoarse - 3, (e / kLabCoarse) % kLabCoarse - 3, e / (kLabCoarse * kLabCoarse) - 3};
-        int code[3];
-        for (int d = 0; d < 3; ++d) code[d] = P[d] < 0 ? -1 : (P[d] > 3 ? 1 : 0);
-        const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
-        const int n = n27[icode];
-        double v = 0.0;
-        if (icode == 13) {
-          double w[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) w[q] = own[((2 * P[2] + (q >> 2)) * 8 + 2 * P[1] + ((q >> 1) & 1)) * 8 + 2 * P[0] + (q & 1)];  // x fastest here
-          v = avg_down8(w);
-        } else if (n >= kNbrCoarser) {
-          v = src[((size_t)(n - kNbrCoarser) * nc + c) * 512 + ((par[2] * 4 + P[2] + 8) & 7) * 64 + ((par[1] * 4 + P[1] + 8) & 7) * 8 + ((par[0] * 4 + P[0] + 8) & 7)];
-        } else if (n >= 0) {
-          v = avg_block(src + ((size_t)n * nc + c) * 512, 2 * P[0] - 8 * code[0], 2 * P[1] - 8 * code[1], 2 * P[2] - 8 * code[2]);
-        }
-        Ct[e] = v;
-      }
-      __syncthreads();
-      // C. domain faces on the coarse tile: the three ghost layers behind the face, every transverse position, from the face cell.
-      //    One pass per axis does both sides: each writes ghosts of its own side and reads the face cells, which no pass writes
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        if (!((dom >> (2 * d)) & 3)) continue;
-        constexpr int per_side = 3 * kLabCoarse * kLabCoarse;
-        const int d1 = (d + 1) % 3, d2 = (d + 2) % 3;
-        for (int i = t; i < 2 * per_side; i += 256) {
-          const int side = i / per_side, j = i - side * per_side;
-          if (!((dom >> (2 * d + side)) & 1)) continue;
-          const int layer = j / (kLabCoarse * kLabCoarse), r = j - layer * (kLabCoarse * kLabCoarse);
-          int p[3], q[3];
-          p[d] = side ? 4 + layer : -1 - layer;
-          q[d] = side ? 3 : 0;
-          p[d1] = q[d1] = r % kLabCoarse - 3;
-          p[d2] = q[d2] = r / kLabCoarse - 3;
-          Ct[cix10(p[0], p[1], p[2])] = lab_bc_value(Ct[cix10(q[0], q[1], q[2])], nc, c, a.bc_comp, a.bc[d], d);
-        }
-        __syncthreads();
-      }
-      // D. ghosts behind coarser neighbours
-      for (int e = t; e < L3; e += 256) {
-        const int l[3] = {e % L - W, (e / L) % L - W, e / (L * L) - W};
-        int code[3], X[3], bit[3], ncode = 0;
-        for (int d = 0; d < 3; ++d) {
-          code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
-          ncode += code[d] != 0;
-          X[d] = l[d] >> 1;   // the coarse cell that holds this fine cell
-          bit[d] = l[d] & 1;  // which of its two children along d
-        }
-        if (ncode == 0 || n27[(code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1)] < kNbrCoarser) continue;
-        const int ax = code[0] ? 0 : (code[1] ? 1 : 2);
-        const int layer = code[ax] < 0 ? -1 - l[ax] : l[ax] - 8;
-        double v;
-        if (ncode == 1 && layer < 2) {  // the two layers next to a face: finite-difference mode
-          const int ax1 = ax == 0 ? 1 : 0, ax2 = ax == 2 ? 1 : 2;
-          const int st1 = ax1 == 0 ? 1 : kLabCoarse, st2 = ax2 == 1 ? kLabCoarse : kLabCoarse * kLabCoarse;
-          const double av = fd_mode_av(Ct + cix10(X[0], X[1], X[2]), X[ax1], X[ax2], st1, st2, bit[ax1], bit[ax2]);
-          int cb[3] = {l[0], l[1], l[2]}, cc[3] = {l[0], l[1], l[2]};
-          cb[ax] = code[ax] > 0 ? 7 : 0;
-          cc[ax] = code[ax] > 0 ? 6 : 1;
-          v = fd_mode_blend(av, lab[lix(cb[0], cb[1], cb[2])], lab[lix(cc[0], cc[1], cc[2])], layer);
-        } else {  // deeper layers, edges and corners: TestInterp
-          v = test_interp([&](int i, int j, int k) -> double { return Ct[cix10(X[0] - 1 + i, X[1] - 1 + j, X[2] - 1 + k)]; }, bit);
-        }
-        lab[e] = v;
-      }
-      __syncthreads();
-    }
-    // E. domain faces on the fine tile: the W ghost layers behind the face, every transverse position (the ghosts earlier passes wrote
-    //    included), from the face cell; one pass per axis, both sides, as on the coarse tile
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      if (!((dom >> (2 * d)) & 3)) continue;
-      constexpr int per_side = W * L * L;
-      const int d1 = (d + 1) % 3, d2 = (d + 2) % 3;
-      for (int i = t; i < 2 * per_side; i += 256) {
-        const int side = i / per_side, j = i - side * per_side;
-        if (!((dom >> (2 * d + side)) & 1)) continue;
-        const int layer = j / (L * L), r = j - layer * (L * L);
-        int p[3], q[3];
-        p[d] = side ? 8 + layer : -1 - layer;
-        q[d] = side ? 7 : 0;
-        p[d1] = q[d1] = r % L - W;
-        p[d2] = q[d2] = r / L - W;
-        lab[lix(p[0], p[1], p[2])] = lab_bc_value(lab[lix(q[0], q[1], q[2])], nc, c, a.bc_comp, a.bc[d], d);
-      }
-      __syncthreads();
-    }
-    // F. the tile leaves in the reference's layout; what the reference leaves undefined leaves as NaN
-    for (int e = t; e < L3; e += 256) {
-      double v = lab[e];
-      if (W <= 2 && star) {
-        const int x = e % L - W, y = (e / L) % L - W, z = e / (L * L) - W;
-        if ((x < 0 || x > 7) + (y < 0 || y > 7) + (z < 0 || z > 7) > 1) v = __builtin_nan("");
-      }
-      tile[(size_t)e * nc + c] = v;
-    }
-    __syncthreads();
-  }
+#define LABS_BLOCK(slot, c) (src + ((size_t)(slot) * nc + (c)) * 512)
+#define LABS_CELL(slot, c, i) src[((size_t)(slot) * nc + (c)) * 512 + (i)]
+#include "labs_body.hpp"
+#undef LABS_BLOCK
+#undef LABS_CELL
+}
+// the same for the local blocks of a rank's tensorial view: tables of the view, ghost blocks in the pool
+template <int W>
+__global__ void __launch_bounds__(256) k_labs_view(LabDev a, const int32_t *__restrict__ slots, int first, int star, LabSrcView src, int nc, double *__restrict__ out) {
+#define LABS_BLOCK(slot, c) src.blk(slot, nc, c)
+#define LABS_CELL(slot, c, i) src.blk(slot, nc, c)[i]
+#include "labs_body.hpp"
+#undef LABS_BLOCK
+#undef LABS_CELL
 }
 
 // ---- host side
@@ -1225,7 +1112,9 @@ struct LabTables {
   double *stage = nullptr;
 };
 
+static void labs_view_destroy(Sim *s);
 void labs_destroy(Sim *s) {
+  labs_view_destroy(s);  // the cached view, its tables and the ghost pool of cup3d_sim_labs_over_ranks
   LabTables *T = s->labs;
   if (!T) return;
   void *dev[] = {T->n27, T->index, T->level, T->finer_row, T->finer, T->d_slots, T->stage};
@@ -1306,19 +1195,19 @@ static int labs_launch(Sim *s, const double *f, int nc, long t0, long m, const i
 }
 
 // the checks both entry points share; nothing is allocated or launched before they pass
-static int labs_check(Sim *s, int field, long n, const int32_t *slots, int width, int scalar_dir, const void *out, const double **f, int *nc) {
-  if (!out) { set_error("cup3d_sim_labs: null output"); return CUP3D_EINVAL; }
+static int labs_check(Sim *s, int field, long n, const int32_t *slots, int width, int scalar_dir, const void *out, const double **f, int *nc, bool over_ranks = false) {
+  if (!out && !(over_ranks && n == 0)) { set_error("cup3d_sim_labs: null output"); return CUP3D_EINVAL; }
   *f = s->field(field, nc);
   if (!*f) { set_error("unknown field id %d", field); return CUP3D_EINVAL; }
   if (width < 1 || width > 4) { set_error("cup3d_sim_labs: width %d; the tiles are pinned for the boxes [-w, w+1), w = 1..4", width); return CUP3D_EINVAL; }
   if (scalar_dir < -1 || scalar_dir > 2) { set_error("cup3d_sim_labs: scalar_dir %d (expected -1, 0, 1 or 2)", scalar_dir); return CUP3D_EINVAL; }
   if (scalar_dir >= 0 && *nc == 3) { set_error("cup3d_sim_labs: scalar_dir %d on a vector field (it selects BlockLabBC<.., direction> for a scalar)", scalar_dir); return CUP3D_EINVAL; }
-  if (s->grid->n_local >= 0 || s->grid->nranks > 1) {
+  if (!over_ranks && (s->grid->n_local >= 0 || s->grid->nranks > 1)) {
     set_error("cup3d_sim_labs: this sim holds one rank's share of a grid spread over %d ranks; tiles whose neighbours live on another rank are out of scope "
-              "(they need the tensorial ghost-block exchange at stencil width)", s->grid->nranks);
+              "(they need the tensorial ghost-block exchange at stencil width: cup3d_sim_labs_over_ranks)", s->grid->nranks);
     return CUP3D_EINVAL;
   }
-  if (n < 0 || (!slots && n != (long)s->nb)) { set_error("cup3d_sim_labs: n = %ld (slots = NULL asks for all %ld local blocks)", n, (long)s->nb); return CUP3D_EINVAL; }
+  if (n < 0 || (!slots && n != (long)s->nb && !(over_ranks && n == 0))) { set_error("cup3d_sim_labs: n = %ld (slots = NULL asks for all %ld local blocks)", n, (long)s->nb); return CUP3D_EINVAL; }
   if (slots)
     for (long i = 0; i < n; ++i)
       if (slots[i] < 0 || slots[i] >= s->nb) { set_error("block slot %d out of range", (int)slots[i]); return CUP3D_EINVAL; }
@@ -1357,4 +1246,283 @@ extern "C" int cup3d_sim_labs(cup3d_sim_t *h, int field, long n, const int32_t *
   }
   stats_field_download((size_t)n * per * sizeof(double));
   return CUP3D_OK;
+}
+
+// ==== cup3d_sim_labs_over_ranks / cup3d_sim_labs_over_ranks_device.  The same tiles when the mesh is spread over ranks: what BlockLabMPI::load
+// (main.cpp:4648-4658) gets from SynchronizerMPI_AMR::fetch (2423-2544).  The sim lives on its rank view of the mesh or on its share of a
+// uniform grid; the tiles are built through the tables of the rank's TENSORIAL view (every same-level, coarser and finer leaf of the
+// 27-point neighbourhood is a ghost slot there), which is derived once per (mesh, owner) and kept in the sim.  Per call:
+//   needs    Grid::lab_boxes replays phases A and B of the kernel (labs_body.hpp) for the requested blocks: per ghost block the box of cells read;
+//   request  one double per ghost block (the box as an exact integer, 0: nothing) travels to the block's owner -- the view's block plan
+//            with the two count vectors swapped -- and comes back to the host, so that owner and receiver know every message's length;
+//   data     the owner packs the boxes (k_pack_boxes), one exchange of nc doubles per cell, the receiver scatters them into a pool that
+//            holds the fetched ghost blocks only (k_unpack_boxes; pool_of[ghost] -> pool row);
+//   tiles    k_labs_view reads local blocks from the sim's field array in place and ghost blocks from the pool.
+// Everything crosses ranks through agree() and exchange_items() (RCCL, the host transport, the in-process test communicator).
+namespace cup3d {
+
+struct DevGrow {  // a device buffer that only grows
+  void *p = nullptr;
+  size_t cap = 0;
+  int need(size_t bytes, Sim *s) {
+    if (bytes <= cap) return CUP3D_OK;
+    if (p) { (void)hipFree(p); s->bytes -= cap; p = nullptr; cap = 0; }
+    CUP3D_HIP(hipMalloc(&p, bytes));
+    cap = bytes;
+    s->bytes += bytes;
+    return CUP3D_OK;
+  }
+  void release(Sim *s) { if (p) { (void)hipFree(p); s->bytes -= cap; } p = nullptr; cap = 0; }
+};
+
+struct LabsView {
+  // the cache key is CONTENT: the leaves of the mesh and the owner of each (a pointer can be freed and reused)
+  std::vector<int32_t> key_level, key_owner;
+  std::vector<int64_t> key_Z;
+  std::unique_ptr<Grid> tv;
+  int32_t *n27 = nullptr, *index = nullptr, *level = nullptr, *finer_row = nullptr, *finer = nullptr;  // tables of k_labs_view (local rows of tv)
+  size_t table_bytes = 0;
+  // one call's plan, host side (members: the uploads read them after the functions that fill them returned) ...
+  std::vector<uint8_t> gbox, sbox, rbox;
+  std::vector<double> h_req, h_got;
+  std::vector<int32_t> pool_of, tile_slots;
+  std::vector<long long> soff, roff;
+  std::vector<int64_t> send_cells, recv_cells;
+  // ... and device side
+  DevGrow d_req, d_got, d_pool_of, d_sslots, d_sbox, d_soff, d_rbox, d_roff, d_pack, d_recv, d_pool, d_slots, d_stage;
+};
+
+static void labs_view_destroy(Sim *s) {
+  LabsView *V = s->labs_view;
+  if (!V) return;
+  void *dev[] = {V->n27, V->index, V->level, V->finer_row, V->finer};
+  for (void *p : dev) if (p) (void)hipFree(p);
+  DevGrow *g[] = {&V->d_req, &V->d_got, &V->d_pool_of, &V->d_sslots, &V->d_sbox, &V->d_soff, &V->d_rbox, &V->d_roff, &V->d_pack, &V->d_recv, &V->d_pool, &V->d_slots, &V->d_stage};
+  for (DevGrow *b : g) b->release(s);
+  s->bytes -= V->table_bytes;
+  delete V;
+  s->labs_view = nullptr;
+}
+
+// the rank's tensorial view of (mesh, owner) with its device tables: the cached one when mesh and owner still say the same
+static int labs_view_get(Sim *s, const Grid *gm, const int32_t *owner, LabsView **out) {
+  const Grid *g = s->grid;
+  const size_t nbg = (size_t)gm->nblocks();
+  LabsView *V = s->labs_view;
+  if (V && V->key_level == gm->blevel && V->key_Z == gm->Z && V->key_owner.size() == nbg && std::equal(V->key_owner.begin(), V->key_owner.end(), owner)) {
+    *out = V;
+    return CUP3D_OK;
+  }
+  labs_view_destroy(s);
+  std::unique_ptr<Grid> tv;
+  std::vector<int32_t> finer_row, finer;
+  try {
+    for (int d = 0; d < 3; ++d)
+      if (gm->bpd[d] != g->bpd[d] || gm->bc[d] != g->bc[d]) throw std::invalid_argument("mesh and sim belong to different boxes");
+    if (gm->level_max != g->level_max) throw std::invalid_argument("mesh and sim belong to different boxes");
+    tv = gm->rank_view(owner, g->rank, g->nranks, /*tensorial=*/true);
+    // the sim's blocks are this rank's leaves of the mesh, one by one and in the same order
+    if (tv->n_local != s->nb) throw std::invalid_argument("the sim does not hold this rank's blocks of the mesh");
+    for (int64_t b = 0; b < s->nb; ++b)
+      if (tv->blevel[b] != (g->multilevel ? g->blevel[b] : g->level) || tv->Z[b] != g->Z[b]) throw std::invalid_argument("the sim's blocks are not this rank's leaves of the mesh (level, Z)");
+    finer_tables(tv.get(), tv->n_local, finer_row, finer);
+  } catch (const std::exception &e) {
+    set_error("cup3d_sim_labs_over_ranks: %s", e.what());
+    return CUP3D_EINVAL;
+  }
+  V = new LabsView();
+  s->labs_view = V;
+  auto up = [&](int32_t **d, const std::vector<int32_t> &v) -> int {
+    CUP3D_HIP(hipMalloc((void **)d, std::max<size_t>(v.size(), 1) * sizeof(int32_t)));
+    if (!v.empty()) CUP3D_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    V->table_bytes += v.size() * sizeof(int32_t);
+    s->bytes += v.size() * sizeof(int32_t);
+    return CUP3D_OK;
+  };
+  int rc;
+  if ((rc = up(&V->n27, tv->nbr27)) || (rc = up(&V->index, tv->index)) || (rc = up(&V->level, tv->blevel)) || (rc = up(&V->finer_row, finer_row)) ||
+      (rc = up(&V->finer, finer))) {
+    labs_view_destroy(s);
+    return rc;
+  }
+  V->key_level = gm->blevel;
+  V->key_Z = gm->Z;
+  V->key_owner.assign(owner, owner + nbg);
+  V->tv = std::move(tv);
+  *out = V;
+  return CUP3D_OK;
+}
+
+// a box of cells of one block as an exact integer (six 4-bit fields; 0: nothing) and back; false: not a box inside a block
+static double box_encode(const uint8_t *b) {
+  return (double)(b[0] | (b[1] << 4) | (b[2] << 8) | (b[3] << 12) | (b[4] << 16) | (b[5] << 20));
+}
+static bool box_decode(double v, uint8_t *b, int64_t *vol) {
+  if (!(v >= 0.0 && v < 16777216.0) || v != (double)(long)v) return false;
+  const long k = (long)v;
+  *vol = 1;
+  for (int i = 0; i < 6; ++i) b[i] = (uint8_t)((k >> (4 * i)) & 15);
+  if (k == 0) { *vol = 0; return true; }
+  for (int d = 0; d < 3; ++d) {
+    if (b[d] >= b[3 + d] || b[3 + d] > 8) return false;
+    *vol *= b[3 + d] - b[d];
+  }
+  return true;
+}
+
+template <class T>
+static int upload_vec(DevGrow &d, const std::vector<T> &v, Sim *s) {
+  int rc = d.need(std::max<size_t>(v.size(), 1) * sizeof(T), s);
+  if (rc) return rc;
+  if (!v.empty()) CUP3D_HIP(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream()));
+  return CUP3D_OK;
+}
+
+static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int32_t *owner, int field, long n, const int32_t *slots, int width, int tensorial,
+                           int scalar_dir, void *out, bool to_host) {
+  if (!h) return CUP3D_EINVAL;  // (without the sim there is no communicator to tell the other ranks through)
+  Sim *s = reinterpret_cast<Sim *>(h);
+  const Grid *gm = reinterpret_cast<const Grid *>(mesh_h);
+  const double *f = nullptr;
+  int nc = 0;
+  LabsView *V = nullptr;
+  // what one rank can get wrong on its own; the ranks agree on the outcome before anything is exchanged
+  auto local_part = [&]() -> int {
+    if (!mesh_h || !owner) { set_error("cup3d_sim_labs_over_ranks: null argument"); return CUP3D_EINVAL; }
+    int rc = labs_check(s, field, n, slots, width, scalar_dir, out, &f, &nc, /*over_ranks=*/true);
+    if (rc) return rc;
+    if (!gm->multilevel || gm->n_local >= 0) { set_error("cup3d_sim_labs_over_ranks needs the GLOBAL mesh object (cup3d_grid_create_mesh), not a rank view"); return CUP3D_EINVAL; }
+    if ((rc = labs_view_get(s, gm, owner, &V))) return rc;
+    const Grid *tv = V->tv.get();
+    try {
+      tv->lab_boxes(n ? slots : nullptr, n, width, V->gbox);
+    } catch (const std::exception &e) {
+      set_error("cup3d_sim_labs_over_ranks: %s", e.what());
+      return CUP3D_EINVAL;
+    }
+    const size_t ng = (size_t)tv->nghost();
+    V->h_req.resize(ng);
+    for (size_t g = 0; g < ng; ++g) V->h_req[g] = box_encode(V->gbox.data() + 6 * g);
+    V->h_got.assign(tv->send_blocks.size(), 0.0);
+    if ((rc = upload_vec(V->d_req, V->h_req, s)) || (rc = V->d_got.need(std::max<size_t>(V->h_got.size(), 1) * sizeof(double), s))) return rc;
+    if (n && slots) {
+      V->tile_slots.assign(slots, slots + n);
+      if ((rc = upload_vec(V->d_slots, V->tile_slots, s))) return rc;
+    }
+    return CUP3D_OK;
+  };
+  int rc = agree(s, local_part(), "cup3d_sim_labs_over_ranks");
+  if (rc) return rc;
+  const Grid *tv = V->tv.get();
+  const int nranks = tv->nranks;
+  const size_t ng = (size_t)tv->nghost(), nsend = tv->send_blocks.size();
+  // ---- request: my ghosts' boxes -> their owners; what comes back is what I have to pack
+  {
+    ProfileScope ps("labs_request");
+    if ((rc = exchange_items(s, (const double *)V->d_req.p, tv->recv_block_count, (double *)V->d_got.p, tv->send_block_count, 1))) return rc;
+    if (nsend) CUP3D_HIP(hipMemcpyAsync(V->h_got.data(), V->d_got.p, nsend * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+  }
+  // ---- the two sides of the data exchange
+  V->send_cells.assign(nranks, 0);
+  V->recv_cells.assign(nranks, 0);
+  std::vector<int32_t> pslots;
+  V->sbox.clear(); V->soff.clear(); V->rbox.clear(); V->roff.clear();
+  V->pool_of.assign(ng, -1);
+  long long so = 0, ro = 0;
+  {
+    size_t i = 0;
+    for (int p = 0; p < nranks; ++p)
+      for (int64_t k = 0; k < tv->send_block_count[p]; ++k, ++i) {
+        uint8_t b[6];
+        int64_t vol;
+        if (!box_decode(V->h_got[i], b, &vol)) { set_error("cup3d_sim_labs_over_ranks: rank %d asked for something that is not a box of cells", p); return CUP3D_ESTATE; }
+        if (!vol) continue;
+        pslots.push_back(tv->send_blocks[i]);
+        V->sbox.insert(V->sbox.end(), b, b + 6);
+        V->soff.push_back(so);
+        so += vol;
+        V->send_cells[p] += vol;
+      }
+  }
+  int32_t nrows = 0;
+  for (size_t g = 0; g < ng; ++g) {
+    const uint8_t *b = V->gbox.data() + 6 * g;
+    const int64_t vol = (int64_t)(b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]);
+    if (!vol) continue;
+    V->pool_of[g] = nrows++;
+    V->rbox.insert(V->rbox.end(), b, b + 6);
+    V->roff.push_back(ro);
+    ro += vol;
+    V->recv_cells[tv->ghost_owner[g]] += vol;
+  }
+  const size_t per = (size_t)nc * 512;
+  const size_t pool_doubles = ((size_t)nrows + 1) * per;
+  {
+    ProfileScope ps("labs_data");
+    if ((rc = upload_vec(V->d_sslots, pslots, s)) || (rc = upload_vec(V->d_sbox, V->sbox, s)) || (rc = upload_vec(V->d_soff, V->soff, s)) ||
+        (rc = upload_vec(V->d_rbox, V->rbox, s)) || (rc = upload_vec(V->d_roff, V->roff, s)) || (rc = upload_vec(V->d_pool_of, V->pool_of, s)) ||
+        (rc = V->d_pack.need(std::max<size_t>((size_t)so * nc, 1) * sizeof(double), s)) || (rc = V->d_recv.need(std::max<size_t>((size_t)ro * nc, 1) * sizeof(double), s)) ||
+        (rc = V->d_pool.need(pool_doubles * sizeof(double), s)))
+      return rc;
+    CUP3D_HIP(hipStreamSynchronize(stream()));  // pslots is a local: its upload has read it
+    if ((rc = launch_pack_boxes(f, (const int32_t *)V->d_sslots.p, (const unsigned char *)V->d_sbox.p, (const long long *)V->d_soff.p, nc, (double *)V->d_pack.p,
+                                (unsigned)pslots.size(), stream())))
+      return rc;
+    if ((rc = exchange_items(s, (const double *)V->d_pack.p, V->send_cells, (double *)V->d_recv.p, V->recv_cells, (size_t)nc))) return rc;
+    // row 0 of the pool is what a ghost block that was not fetched reads as: NaN.  "poison_ghosts" (tests): so does every cell of a
+    // fetched block that did not travel, as after the star exchange
+    if ((rc = launch_nan_fill((double *)V->d_pool.p, debug_option("poison_ghosts") ? pool_doubles : per, stream()))) return rc;
+    if ((rc = launch_unpack_boxes((double *)V->d_pool.p + per, (const unsigned char *)V->d_rbox.p, (const long long *)V->d_roff.p, nc, (const double *)V->d_recv.p,
+                                  (unsigned)nrows, stream())))
+      return rc;
+  }
+  // ---- tiles
+  if (n == 0) {
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    return CUP3D_OK;
+  }
+  const Grid *g = s->grid;
+  LabDev a{V->n27, V->index, V->level, V->finer_row, V->finer, {g->bpd[0], g->bpd[1], g->bpd[2]}, {g->bc[0], g->bc[1], g->bc[2]}, nc == 1 ? scalar_dir : -1};
+  LabSrcView src{f, (const double *)V->d_pool.p, (const int32_t *)V->d_pool_of.p, (int)tv->n_local};
+  const int star = tensorial ? 0 : 1;
+  const size_t L = 8 + 2 * (size_t)width, tile = L * L * L * nc;
+  long cap = n;
+  if (to_host) {
+    if ((rc = V->d_stage.need(std::min<size_t>(kLabStageBytes, (size_t)n * tile * sizeof(double)), s))) return rc;
+    cap = std::max<long>(1, (long)(kLabStageBytes / (tile * sizeof(double))));
+  }
+  for (long t0 = 0; t0 < n; t0 += cap) {  // the host variant goes through its bounded staging buffer chunk by chunk
+    const long m = std::min(cap, n - t0);
+    double *dst = to_host ? (double *)V->d_stage.p : (double *)out + (size_t)t0 * tile;
+    const int32_t *sl = slots ? (const int32_t *)V->d_slots.p + t0 : nullptr;
+    {
+      ProfileScope ps("labs_view");
+      switch (width) {
+        case 1: hipLaunchKernelGGL(k_labs_view<1>, dim3((unsigned)m), dim3(256), 0, stream(), a, sl, (int)t0, star, src, nc, dst); break;
+        case 2: hipLaunchKernelGGL(k_labs_view<2>, dim3((unsigned)m), dim3(256), 0, stream(), a, sl, (int)t0, star, src, nc, dst); break;
+        case 3: hipLaunchKernelGGL(k_labs_view<3>, dim3((unsigned)m), dim3(256), 0, stream(), a, sl, (int)t0, star, src, nc, dst); break;
+        default: hipLaunchKernelGGL(k_labs_view<4>, dim3((unsigned)m), dim3(256), 0, stream(), a, sl, (int)t0, star, src, nc, dst); break;
+      }
+    }
+    CUP3D_HIP(hipGetLastError());
+    if (to_host) {
+      CUP3D_HIP(hipMemcpyAsync((double *)out + (size_t)t0 * tile, V->d_stage.p, (size_t)m * tile * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipStreamSynchronize(stream()));
+    }
+  }
+  if (to_host) stats_field_download((size_t)n * tile * sizeof(double));
+  return CUP3D_OK;
+}
+
+}  // namespace cup3d
+
+extern "C" int cup3d_sim_labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh, const int32_t *owner, int field, long n, const int32_t *slots, int width,
+                                         int tensorial, int scalar_dir, double *host_out) {
+  return labs_over_ranks(h, mesh, owner, field, n, slots, width, tensorial, scalar_dir, host_out, true);
+}
+
+extern "C" int cup3d_sim_labs_over_ranks_device(cup3d_sim_t *h, const cup3d_grid_t *mesh, const int32_t *owner, int field, long n, const int32_t *slots, int width,
+                                                int tensorial, int scalar_dir, void *device_out) {
+  return labs_over_ranks(h, mesh, owner, field, n, slots, width, tensorial, scalar_dir, device_out, false);
 }

@@ -310,6 +310,24 @@ __global__ void __launch_bounds__(256) k_poison(double *__restrict__ p, size_t n
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = __builtin_nan("");
 }
 
+// the same three kernels for a caller in another file (cup3d_sim_labs_over_ranks, amr.hip: boxes asked for per call, a pool of ghost
+// blocks instead of the ghost slots of a field): n blocks of `nc` components each, on stream st
+int launch_pack_boxes(const double *field, const int32_t *slots, const unsigned char *box, const long long *off, int nc, double *out, unsigned n, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_pack_boxes, dim3(n), dim3(256), 0, st, field, slots, box, off, nc, out);
+  CUP3D_HIP(hipGetLastError());
+  return CUP3D_OK;
+}
+int launch_unpack_boxes(double *blocks, const unsigned char *box, const long long *off, int nc, const double *in, unsigned n, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_unpack_boxes, dim3(n), dim3(256), 0, st, blocks, box, off, nc, in);
+  CUP3D_HIP(hipGetLastError());
+  return CUP3D_OK;
+}
+int launch_nan_fill(double *p, size_t n, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_poison, dim3((unsigned)std::min<size_t>(256, (n + 255) / 256)), dim3(256), 0, st, p, n);
+  CUP3D_HIP(hipGetLastError());
+  return CUP3D_OK;
+}
+
 // items of `per` doubles: packed send buffer -> peers; received runs land contiguously at dst.  RCCL on the communication stream
 // (compute stream <-> communication stream hand-off by events), or the in-process transport.
 static size_t sent_bytes(const std::vector<int64_t> &send_count, size_t per, int skip = -1) {

@@ -330,6 +330,92 @@ static void star_boxes(const Grid &G, const int32_t *owner, int r, int W, std::m
   }
 }
 
+// The tile consumers' counterpart of star_boxes, on a tensorial rank view (grid.hpp): phases A and B of the tile kernels (labs_body.hpp) are the only
+// ones that read blocks -- C to F work on the two tiles in LDS -- and they are replayed here cell by cell with the kernel's own
+// expressions, so that a change there has one place to be repeated in.  Blocks whose 27 positions are all local are skipped.
+void Grid::lab_boxes(const int32_t *slots, int64_t n, int W, std::vector<uint8_t> &box) const {
+  if (n_local < 0 || !multilevel) throw std::invalid_argument("lab_boxes needs a rank view");
+  if (W < 1 || W > 4) throw std::invalid_argument("lab_boxes: width outside 1..4");
+  const int64_t ng = nghost();
+  std::vector<CellBox> bx((size_t)ng);
+  auto mark = [&](int32_t slot, const int lo[3], const int hi[3]) {
+    if (slot < n_local) return;
+    if (slot >= n_local + ng) throw std::logic_error("lab_boxes: a tile reads a block that is not visible");
+    CellBox &b = bx[(size_t)(slot - n_local)];
+    for (int d = 0; d < 3; ++d) {
+      if (lo[d] < 0 || hi[d] > 8 || lo[d] >= hi[d]) throw std::logic_error("lab_boxes: a tile's cell range leaves the block");
+      b.lo[d] = (uint8_t)std::min<int>(b.lo[d], lo[d]);
+      b.hi[d] = (uint8_t)std::max<int>(b.hi[d], hi[d]);
+    }
+  };
+  constexpr int kC = 10;  // kLabCoarse: the coarse shadow tile holds coarse cells [-3, 7)^3
+  const int L = 8 + 2 * W, L3 = L * L * L, C3 = kC * kC * kC;
+  std::vector<char> done((size_t)n_local, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t pb = slots ? slots[i] : (int32_t)i;
+    if (pb < 0 || pb >= n_local) throw std::invalid_argument("lab_boxes: block slot out of range");
+    if (done[pb]) continue;
+    done[pb] = 1;
+    const int32_t *n27 = nbr27.data() + 27 * (size_t)pb;
+    bool remote = false, has_coarse = false;
+    for (int c = 0; c < 27; ++c) {
+      const int32_t v = n27[c];
+      if (v >= kNbrCoarser) { has_coarse = true; remote = remote || v - kNbrCoarser >= n_local; }
+      else if (v >= n_local || v == kNbrFiner) remote = true;
+    }
+    if (!remote) continue;
+    const int idx[3] = {index[3 * (size_t)pb], index[3 * (size_t)pb + 1], index[3 * (size_t)pb + 2]};
+    const int par[3] = {idx[0] & 1, idx[1] & 1, idx[2] & 1};
+    const int lev = blevel[pb];
+    // A. same-level neighbours (copied), finer neighbours (averaged down)
+    for (int e = 0; e < L3; ++e) {
+      const int l[3] = {e % L - W, (e / L) % L - W, e / (L * L) - W};
+      int code[3], loc[3], fl[3], fi[3];
+      for (int d = 0; d < 3; ++d) {
+        code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
+        loc[d] = l[d] - 8 * code[d];
+        fl[d] = code[d] < 0 ? 8 + 2 * l[d] : (code[d] > 0 ? 2 * (l[d] - 8) : (2 * l[d]) & 7);
+        fi[d] = 2 * idx[d] + (code[d] < 0 ? -1 : (code[d] > 0 ? 2 : (l[d] >= 4 ? 1 : 0)));  // the octant's leaf, as finer_tables names it
+      }
+      const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
+      if (icode == 13) continue;
+      const int32_t v = n27[icode];
+      if (v >= 0 && v < kNbrCoarser) {
+        const int hi[3] = {loc[0] + 1, loc[1] + 1, loc[2] + 1};
+        mark(v, loc, hi);
+      } else if (v == kNbrFiner) {
+        const int32_t fs = leaf(lev + 1, fi);
+        const int hi[3] = {fl[0] + 2, fl[1] + 2, fl[2] + 2};
+        if (fs >= 0) mark(fs, fl, hi);
+      }
+    }
+    if (!has_coarse) continue;
+    // B. the coarse shadow tile: cells of coarser leaves, 2x2x2 averages of same-level neighbours
+    for (int e = 0; e < C3; ++e) {
+      const int P[3] = {e % kC - 3, (e / kC) % kC - 3, e / (kC * kC) - 3};
+      int code[3];
+      for (int d = 0; d < 3; ++d) code[d] = P[d] < 0 ? -1 : (P[d] > 3 ? 1 : 0);
+      const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
+      if (icode == 13) continue;
+      const int32_t v = n27[icode];
+      int lo[3], hi[3];
+      if (v >= kNbrCoarser) {
+        for (int d = 0; d < 3; ++d) { lo[d] = (par[d] * 4 + P[d] + 8) & 7; hi[d] = lo[d] + 1; }
+        mark(v - kNbrCoarser, lo, hi);
+      } else if (v >= 0) {
+        for (int d = 0; d < 3; ++d) { lo[d] = 2 * P[d] - 8 * code[d]; hi[d] = lo[d] + 2; }
+        mark(v, lo, hi);
+      }
+    }
+  }
+  box.assign(6 * (size_t)ng, 0);
+  for (int64_t g = 0; g < ng; ++g) {
+    const CellBox &b = bx[(size_t)g];
+    if (b.lo[0] >= b.hi[0]) continue;
+    for (int d = 0; d < 3; ++d) { box[6 * g + d] = b.lo[d]; box[6 * g + 3 + d] = b.hi[d]; }
+  }
+}
+
 std::unique_ptr<Grid> Grid::rank_view(const int32_t *owner, int rank_, int nranks_, bool tensorial) const {
   if (!multilevel || n_local >= 0) throw std::invalid_argument("rank_view needs a global multi-level mesh");
   if (!owner || nranks_ < 1 || rank_ < 0 || rank_ >= nranks_) throw std::invalid_argument("bad rank / nranks");

@@ -150,6 +150,13 @@ struct Grid {
   // tensorial: also the finer leaves behind EDGE and CORNER positions become ghosts -- what the tensorial [-1,2) tile of mesh adaptation
   // (refine_1 / RefineBlocks) averages down; the star-shaped stencils of the time step never read them
   std::unique_ptr<Grid> rank_view(const int32_t *owner, int rank, int nranks, bool tensorial = false) const;
+  // Tensorial rank views: the cells of GHOST blocks that the ghosted tiles [-w, w+1)^3 of the local blocks `slots` (nullptr: all n_local
+  // of them; repeats allowed) read -- k_labs' index arithmetic (amr.hip) replayed on the host, as star_boxes replays the star consumers:
+  // the w layers of a same-level neighbour (one, two or three axes off centre), the 2w layers of a finer leaf that AverageDown reads,
+  // and -- for a block with a coarser neighbour anywhere -- what its coarse shadow tile [-3, 7)^3 takes: cells of coarser leaves, 2x2x2
+  // averages over same-level neighbours.  box[nghost][6]: the union over the tiles as one bounding box per ghost block, lo x, y, z,
+  // hi x, y, z (hi exclusive; all zero: nothing of that block is read).  What cup3d_sim_labs_over_ranks asks the owners for.
+  void lab_boxes(const int32_t *slots, int64_t n, int w, std::vector<uint8_t> &box) const;
   // the multigrid hierarchy of rank `rank` when the leaves of this (global, multi-level) mesh are owned as `owner` says (nullptr: one
   // rank owns everything); leaf_slot[global leaf] = slot of the leaf in that rank's field arrays (nullptr: the global slot itself)
   std::shared_ptr<MGHierarchy> mg_hierarchy(const int32_t *owner, int rank, int nranks, const std::vector<int32_t> *leaf_slot) const;

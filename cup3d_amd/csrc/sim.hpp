@@ -137,6 +137,7 @@ struct Sim {
   unsigned *h_early_fail = nullptr, *h_early_fail_dev = nullptr;  // pinned: a bounded device-side wait of the early all-reduce gave up
   void *mg = nullptr;              // level hierarchy of the multigrid preconditioner (multigrid.hip), built on first use
   struct LabTables *labs = nullptr;  // tables and staging buffer of cup3d_sim_labs (amr.hip), built on first use
+  struct LabsView *labs_view = nullptr;  // cup3d_sim_labs_over_ranks: the rank's tensorial view, its tables, the ghost pool (amr.hip)
   int max_groups = 0;
   // staging for host transfers
   double *d_stage = nullptr;
@@ -209,6 +210,11 @@ int view_exchange_flux(Sim *s, int nfc);
 int view_exchange_blocks(Sim *s, double *field, int nc, int w);  // w: width of the star stencil that will read them (1 or 3)
 // generic exchange of `per`-double items between ranks (own rank included), peer-major buffers; compute stream
 int exchange_items(Sim *s, const double *sendbuf, const std::vector<int64_t> &send_count, double *recvbuf, const std::vector<int64_t> &recv_count, size_t per);
+// the sub-box pack / unpack kernels of the ghost-block exchange and the NaN fill of "poison_ghosts" for a caller outside comm.hip:
+// block i of `slots` contributes the cells of box[i] at offset off[i] * nc of the message; they arrive in box[i] of block row i
+int launch_pack_boxes(const double *field, const int32_t *slots, const unsigned char *box, const long long *off, int nc, double *out, unsigned n, hipStream_t st);
+int launch_unpack_boxes(double *blocks, const unsigned char *box, const long long *off, int nc, const double *in, unsigned n, hipStream_t st);
+int launch_nan_fill(double *p, size_t n_doubles, hipStream_t st);
 void vcomm_register(Sim *s);    // in-process test communicator (comm.hip)
 void vcomm_unregister(Sim *s);
 
@@ -226,7 +232,7 @@ int launch_mean_total(Sim *s);  // total of the block sums in d_partials' tail -
 // block_solver 5: one multigrid V-cycle from a zero guess as M^-1 (multigrid.hip; an alternative, not the reference's algorithm)
 int mg_vcycle(Sim *s, const double *in, double *out);
 void mg_destroy(Sim *s);
-void labs_destroy(Sim *s);  // what cup3d_sim_labs built on first use (amr.hip)
+void labs_destroy(Sim *s);  // what cup3d_sim_labs and cup3d_sim_labs_over_ranks built on first use (amr.hip)
 // implicit diffusion (DiffusionSolver, main.cpp:6719-7147): Helmholtz operator of velocity component `direction`
 struct HelmholtzOp { int direction; double dt, nu; };
 int launch_lhs_diffusion(Sim *s, const double *p, double *out, const HelmholtzOp &op);

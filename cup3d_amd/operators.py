@@ -122,6 +122,20 @@ class Grid:
             glob[8 * k:8 * k + 8, 8 * j:8 * j + 8, 8 * i:8 * i + 8] = blocks[s]
 
 
+def uniform_share_mesh(bpd, levelMax, level, maxextent, bc, nranks):
+    """What labs_over_ranks needs beside the sims of a uniform grid spread over `nranks` ranks (SimulationData(rank=r, nranks=nranks, ...)):
+    the same level as a one-level mesh object, and the owner of each of its leaves -- the contiguous Z-range partition of GridMPI
+    (main.cpp:2959-2986), read off the ranks' own Grid objects.  Host only; build it once and pass it to every call.  Returns (mesh, owner)."""
+    whole = Grid(bpd, levelMax, level, maxextent, bc)
+    mesh = Grid(bpd, levelMax, 0, maxextent, bc, leaves=(whole.tables[:, 0].astype(np.int32), whole.tables[:, 1].copy()))
+    rank_of_z = {}
+    for r in range(nranks):
+        for z in Grid(bpd, levelMax, level, maxextent, bc, r, nranks).tables[:, 1]:
+            rank_of_z[int(z)] = r
+    owner = np.array([rank_of_z[int(z)] for z in mesh.tables[:, 1]], dtype=np.int32)
+    return mesh, owner
+
+
 class RankView:
     """One rank's view of a multi-level mesh whose leaves are spread over ranks (Grid.rank_view): local blocks, ghost blocks, interface
     faces, neighbour tables in the view's slot numbering, and the two exchange plans (whole ghost blocks before a stencil kernel,
@@ -300,6 +314,28 @@ class SimulationData:
         fid, sl, n, shape = self._labs_args(field, width, slots)
         check(lib().cup3d_sim_labs_device(self.handle, fid, n, None if sl is None else sl.ctypes.data_as(C.c_void_p), int(width),
                                           int(bool(tensorial)), int(scalar_dir), C.c_void_p(int(ptr))))
+        return shape
+
+    def labs_over_ranks(self, field, width, mesh, owner, tensorial=False, slots=None, scalar_dir=-1):
+        """labs() when the mesh is spread over ranks (cup3d_sim_labs_over_ranks; BlockLabMPI::load, main.cpp:4648-4658).  mesh / owner:
+        the GLOBAL mesh object (a Grid built with leaves=...) and the rank of every leaf; this SimulationData lives on this rank's view of
+        it (view=...) or on its share of a uniform grid (rank=, nranks=: see uniform_share_mesh).  slots: local slots; None: every
+        local block; an empty list: this rank needs nothing.  COLLECTIVE: every rank calls it with the same field, width and tensorial."""
+        fid, sl, n, shape = self._labs_args(field, width, slots)
+        ow = np.ascontiguousarray(owner, dtype=np.int32)
+        out = np.empty(shape)
+        check(lib().cup3d_sim_labs_over_ranks(self.handle, mesh.handle, ow.ctypes.data_as(C.c_void_p), fid, n, None if sl is None else sl.ctypes.data_as(C.c_void_p),
+                                              int(width), int(bool(tensorial)), int(scalar_dir), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def labs_over_ranks_into(self, ptr, field, width, mesh, owner, tensorial=False, slots=None, scalar_dir=-1):
+        """The same into device memory at `ptr` (n*L^3*nc doubles; may be 0 for an empty slot list), stream-ordered on the library's
+        compute stream behind the exchange (cup3d_sim_labs_over_ranks_device).  Returns the shape of the tiles written."""
+        fid, sl, n, shape = self._labs_args(field, width, slots)
+        ow = np.ascontiguousarray(owner, dtype=np.int32)
+        check(lib().cup3d_sim_labs_over_ranks_device(self.handle, mesh.handle, ow.ctypes.data_as(C.c_void_p), fid, n,
+                                                     None if sl is None else sl.ctypes.data_as(C.c_void_p), int(width), int(bool(tensorial)), int(scalar_dir),
+                                                     C.c_void_p(int(ptr)) if ptr else None))
         return shape
 
     def _like(self, **kw):

@@ -197,9 +197,29 @@ CUP3D_API int cup3d_sim_download_block_list(cup3d_sim_t *, int field, long n, co
  * cup3d_run_stats.field_bytes_downloaded and synchronises before it returns; the device variant is stream-ordered and does not.
  * CUP3D_EINVAL, nothing touched: width outside 1..4, unknown field, NULL output, slot outside [0, nblocks), n != nblocks with
  * slots = NULL, scalar_dir >= 0 on a vector field, a sim on a rank view or on one rank's share of a uniform grid (tiles whose
- * neighbours live on another rank are out of scope). */
+ * neighbours live on another rank come from cup3d_sim_labs_over_ranks below). */
 CUP3D_API int cup3d_sim_labs(cup3d_sim_t *, int field, long n, const int32_t *slots, int width, int tensorial, int scalar_dir, double *host_out);
 CUP3D_API int cup3d_sim_labs_device(cup3d_sim_t *, int field, long n, const int32_t *slots, int width, int tensorial, int scalar_dir, void *device_out);
+/* The same tiles on a mesh spread over ranks: what BlockLabMPI::load (main.cpp:4648-4658) gets from SynchronizerMPI_AMR::fetch
+ * (2423-2544).  mesh / owner: the GLOBAL multi-level mesh object and the rank of every leaf, as for cup3d_adapt_migrate; the sim is this
+ * rank's, on its cup3d_grid_rank_view of that mesh or on its share of a uniform grid (cup3d_grid_create_uniform(.., rank, nranks): pass
+ * the same level as a one-level mesh from cup3d_grid_create_mesh, owner = the contiguous Z-range partition).  slots are LOCAL slots of
+ * the sim exactly as for cup3d_sim_labs (NULL with n = nblocks: every local block; repeated and unordered slots allowed); width,
+ * tensorial, scalar_dir, the tile layout and the NaN cells of star tiles are those of cup3d_sim_labs, and a tile does not depend on how
+ * the mesh is partitioned.  COLLECTIVE: every rank of the communicator calls it with the same field, width and tensorial and its own
+ * n / slots; a rank that needs nothing passes n = 0 (slots and the output may then be NULL).  Only what the requested tiles read
+ * travels, and of each remote block only the bounding box of the cells read: per call each rank sends every owner one double per ghost
+ * block of its tensorial view (the box, 0 for nothing), then the owners send the boxes' cells; both count in
+ * cup3d_run_stats.halo_bytes_sent.  The view and its tables are kept in the sim between calls while mesh and owner say the same
+ * (compared by content).  Errors one rank can find on its own -- NULL mesh / owner, a rank view in `mesh`'s place, an owner out of range,
+ * a bad width / field / slot / scalar_dir, a sim whose local blocks are not, (level, Z) by (level, Z), this rank's leaves of `mesh` -- are
+ * agreed over the ranks before anything is exchanged: every rank returns the failure and nothing has been touched.  The call waits for
+ * the received requests on the host; the device variant's tiles are stream-ordered on the compute stream behind that.  On one rank
+ * both give what cup3d_sim_labs gives. */
+CUP3D_API int cup3d_sim_labs_over_ranks(cup3d_sim_t *, const cup3d_grid_t *mesh, const int32_t *owner, int field, long n, const int32_t *slots, int width,
+                                        int tensorial, int scalar_dir, double *host_out);
+CUP3D_API int cup3d_sim_labs_over_ranks_device(cup3d_sim_t *, const cup3d_grid_t *mesh, const int32_t *owner, int field, long n, const int32_t *slots,
+                                               int width, int tensorial, int scalar_dir, void *device_out);
 CUP3D_API int cup3d_sim_upload(cup3d_sim_t *, int field, const double *blocks);
 CUP3D_API int cup3d_sim_download(cup3d_sim_t *, int field, double *blocks);
 CUP3D_API int cup3d_sim_fill(cup3d_sim_t *, int field, double value);

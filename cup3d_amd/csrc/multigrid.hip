@@ -72,11 +72,13 @@ static const char *level_name(int kind, int level) {
 struct Multigrid {
   std::vector<MGLevel> lev;  // [0] coarsest ... [L] finest
   double *zeros = nullptr;   // ghost values behind faces owned by other ranks (see mg_setup); the x pointer itself on one rank
+  double *staged = nullptr;  // uniform grids, in == out (cup3d_preconditioner): the finest level's right-hand side, copied there before the cycle
   bool local = false;        // a rank-local hierarchy (several ranks)
   bool amr = false;          // hierarchy of a multi-level mesh (mg_setup_amr)
   std::shared_ptr<const MGHierarchy> plan;  // ... its tables (kept alive: the exchange plans are read at every cycle)
   ~Multigrid() {
     if (zeros) hipFree(zeros);
+    if (staged) hipFree(staged);
     for (size_t i = 0; i < lev.size(); ++i) {
       MGLevel &l = lev[i];
       if ((l.grid || l.own_nbr) && l.d_nbr) hipFree(l.d_nbr);
@@ -608,13 +610,25 @@ static int mg_vcycle_amr(Sim *s, Multigrid &mg, const double *in, double *out, i
   return CUP3D_OK;
 }
 
-// out = V-cycle(in) from a zero guess; `in` is not modified
+// out = V-cycle(in) from a zero guess; `in` is not modified unless in == out.  On a uniform grid `out` is the finest level's iterate
+// buffer and `in` its right-hand side for the whole cycle, so an in-place call (cup3d_preconditioner; the solver never makes one) has its
+// input staged in a buffer of the hierarchy's first: allocated by the first such call, no copy and no launch on any other path.
+// mg_vcycle_amr gathers `in` into the levels' own b before it writes anything and needs none.
 int mg_vcycle(Sim *s, const double *in, double *out) {
   int rc = mg_setup(s);
   if (rc) return rc;
   Multigrid &mg = *reinterpret_cast<Multigrid *>(s->mg);
   if (mg.amr) return mg_vcycle_amr(s, mg, in, out, debug_option("mg_launches") > 0 ? debug_option("mg_launches") : 2, debug_option("mg_sweeps") > 0 ? debug_option("mg_sweeps") : 2);
   const int L = (int)mg.lev.size() - 1;
+  if (in == out) {
+    const size_t bytes = (size_t)std::max<int64_t>(s->nb, 1) * 512 * sizeof(double);
+    if (!mg.staged) {
+      CUP3D_HIP(hipMalloc((void **)&mg.staged, bytes));
+      s->bytes += bytes;
+    }
+    if (s->nb) CUP3D_HIP(hipMemcpyAsync(mg.staged, in, (size_t)s->nb * 512 * sizeof(double), hipMemcpyDeviceToDevice, stream()));
+    in = mg.staged;
+  }
   // smoothing launches before / after the coarse-grid correction, sweeps per launch (ghosts are frozen within a launch);
   // cup3d_debug_set_option("mg_launches" / "mg_sweeps") for tuning scans
   const int nu = debug_option("mg_launches") > 0 ? debug_option("mg_launches") : 2, sw = debug_option("mg_sweeps") > 0 ? debug_option("mg_sweeps") : 2;

@@ -732,7 +732,9 @@ int cup3d_preconditioner(cup3d_sim_t *h, int block_solver) {
   if (!h) return CUP3D_EINVAL;
   Sim *s = reinterpret_cast<Sim *>(h);
   s->block_solver = block_solver;
-  return launch_precond(s, s->pres, s->pres, false);  // in place: each wavefront reads its block before writing it
+  // in place: a block solve reads its block before it writes it; the multigrid cycle of a uniform grid, whose output doubles as the
+  // finest iterate while the input is read again by every launch, stages its input first (mg_vcycle)
+  return launch_precond(s, s->pres, s->pres, false);
 }
 
 int cup3d_poisson_path_checksum(cup3d_sim_t *h, int block_solver, int mean_constraint, unsigned long long *sums) {

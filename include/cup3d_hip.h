@@ -290,7 +290,8 @@ CUP3D_API void cup3d_poisson_default_params(cup3d_poisson_params *);
 /* ComputeLHS::operator() (main.cpp:9273-9327): lhs = h*(sum6 - 6p) of pres + mean constraint */
 CUP3D_API int cup3d_compute_lhs(cup3d_sim_t *, int mean_constraint);
 /* poisson_kernels::getZImplParallel (main.cpp:14704-14745): block preconditioner on pres, in place;
- * block_solver as in cup3d_poisson_params */
+ * block_solver as in cup3d_poisson_params -- EVERY value works in place, 5 (one multigrid V-cycle) included: pres holds M^-1 of
+ * what it held, on uniform grids and multi-level meshes, on one rank and over ranks */
 CUP3D_API int cup3d_preconditioner(cup3d_sim_t *, int block_solver);
 /* PoissonSolverBase::solve() (main.cpp:8921-8928; PoissonSolverAMR::solve 14363-14616):
  * RHS in lhs, initial guess and result in pres; lhs is clobbered. */

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import cup3d_amd as cu
+import multigrid_cases as K
 import oracle_lib as O
 from cup3d_amd.capi import check, lib
 
@@ -177,17 +178,7 @@ def test_uniform_grid_default_tolerance_over_ranks():
 
 
 # ------------------------------------------------------------------ multi-level meshes spread over ranks (rank views)
-def _mesh_case(name):
-    if name == "l012_wall":
-        bpd, lmax, bc = (2, 2, 2), 3, ("wall", "freespace", "wall")
-        lv, zs = O.build_balanced_mesh(bpd, lmax, bc, [(0, 0, 0, 0), (1, 0, 0, 0)])
-    elif name == "l012_periodic":
-        bpd, lmax, bc = (2, 2, 2), 3, ("periodic", "periodic", "periodic")
-        lv, zs = O.build_balanced_mesh(bpd, lmax, bc, [(0, 1, 1, 1), (1, 2, 2, 2), (1, 3, 3, 3)])
-    else:  # a non-cubic box, mixed boundary conditions
-        bpd, lmax, bc = (3, 2, 2), 3, ("periodic", "wall", "freespace")
-        lv, zs = O.build_balanced_mesh(bpd, lmax, bc, [(0, 2, 1, 0), (1, 4, 2, 1), (0, 0, 0, 1)])
-    return bpd, lmax, bc, lv, zs
+_mesh_case = K.mesh_case   # the three three-level meshes (shared with the V-cycle tests: tests/multigrid_cases.py)
 
 
 def _owners(nb, nranks, kind, seed=0):
@@ -720,6 +711,38 @@ def test_multigrid_preconditioner_coupled_over_ranks(nranks, level):
     corr = np.abs(vel_one - velg).max()
     assert np.abs(got_pres - pres_one).max() <= 1e-6 * np.abs(pres_one).max()
     assert np.abs(got_vel - vel_one).max() <= 1e-6 * corr
+
+
+@pytest.mark.parametrize("nranks", [2, 4])
+def test_multigrid_cycle_over_ranks_equals_the_restatement(nranks):
+    """ONE application of the uniform V-cycle coupled over ranks (cup3d_preconditioner(sim, 5) on every rank, in place) against the dense
+    NumPy restatement in longdouble -- the first check of this cycle over ranks against anything but itself.  (1,1,1) level 2, walls: the
+    partition of 2 or 4 ranks nests down to level 1 and no further, so the restatement's hierarchy has depth 2, its coarsest level (8
+    blocks) takes 16 x 4 and loses its mean over ALL cells (one all-reduce on the device).  Tolerance as in tests/test_gpu_multigrid_cycle.py:
+    32 x max(|z_f64 - z_ld|, 4 eps max|z_ld|); observed ratio 1.11 on 2 and on 4 ranks."""
+    bpd, level, bc = K.RANKS_CASE
+    r, (z64, zld) = K.restated_uniform("ranks", "random", depth=2, coarsest=(16, 4))
+    kw = dict(bpdx=bpd[0], bpdy=bpd[1], bpdz=bpd[2], levelMax=level + 1, levelStart=level, extent=EXT, BC_x=bc[0], BC_y=bc[1], BC_z=bc[2], blockSolver=5)
+    out = {}
+    with VirtualComm(nranks):
+        sims = [cu.SimulationData(rank=q, nranks=nranks, **kw) for q in range(nranks)]
+
+        def rank(q):
+            s = sims[q]
+            s.upload("pres", s.grid.to_blocks(r))
+            check(lib().cup3d_preconditioner(s.handle, 5))
+            out[q] = s.download("pres")
+
+        run_ranks(rank, nranks)
+        z = np.full_like(r, np.nan)
+        for q, s in enumerate(sims):
+            s.grid.scatter_to_global(out[q], z)
+        del sims
+    assert np.isfinite(z).all()
+    unit = K.tolerance(z64, zld) / K.MARGIN
+    err = float(np.abs(z - zld).max())
+    print(f"V-cycle over {nranks} ranks: max|z_dev - z_ld| = {err:.3e} = {err / unit:.2f} x max(|z_f64 - z_ld|, 4 eps |z_ld|) (bound {K.MARGIN})")
+    assert err <= K.MARGIN * unit
 
 
 @pytest.mark.parametrize("nranks", [2, 3])

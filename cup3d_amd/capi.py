@@ -60,6 +60,12 @@ class Obstacle(C.Structure):
                 ("force", C.c_double * 3), ("torque", C.c_double * 3)]
 
 
+class ObstacleSurface(C.Structure):
+    """cup3d_obstacle_surface"""
+    _fields_ = [("nblocks", C.c_long), ("slots", C.c_void_p), ("first", C.c_void_p), ("ijk", C.c_void_p), ("dchi", C.c_void_p), ("udef", C.c_void_p),
+                ("cm", C.c_double * 3), ("vel", C.c_double * 3), ("omega", C.c_double * 3), ("points", C.c_void_p), ("qoi", C.c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/cup3d_hip.h
 SIGNATURES = {
     "cup3d_last_error": (C.c_char_p, []),
@@ -146,6 +152,8 @@ SIGNATURES = {
     "cup3d_diffusion_solve": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.POINTER(PoissonParams), C.POINTER(PoissonResult)]),
     "cup3d_penalization": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Obstacle)]),
     "cup3d_update_tmpv": (C.c_int, [_vp, C.c_int, C.POINTER(Obstacle)]),
+    "cup3d_compute_forces": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
+    "cup3d_compute_forces_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_profile_enable": (C.c_int, [C.c_int]),
     "cup3d_profile_reset": (C.c_int, []),
     "cup3d_profile_read": (C.c_int, [C.POINTER(ProfileEntry), C.c_int, C.POINTER(C.c_int)]),

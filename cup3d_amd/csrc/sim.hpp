@@ -138,6 +138,7 @@ struct Sim {
   void *mg = nullptr;              // level hierarchy of the multigrid preconditioner (multigrid.hip), built on first use
   struct LabTables *labs = nullptr;  // tables and staging buffer of cup3d_sim_labs (amr.hip), built on first use
   struct LabsView *labs_view = nullptr;  // cup3d_sim_labs_over_ranks: the rank's tensorial view, its tables, the ghost pool (amr.hip)
+  struct ForcesScratch *forces = nullptr;  // cup3d_compute_forces: tile scratch and staged surface arrays, grow-only (obstacles.hip)
   int max_groups = 0;
   // staging for host transfers
   double *d_stage = nullptr;
@@ -233,6 +234,7 @@ int launch_mean_total(Sim *s);  // total of the block sums in d_partials' tail -
 int mg_vcycle(Sim *s, const double *in, double *out);
 void mg_destroy(Sim *s);
 void labs_destroy(Sim *s);  // what cup3d_sim_labs and cup3d_sim_labs_over_ranks built on first use (amr.hip)
+void forces_destroy(Sim *s);  // the scratch of cup3d_compute_forces (obstacles.hip)
 // implicit diffusion (DiffusionSolver, main.cpp:6719-7147): Helmholtz operator of velocity component `direction`
 struct HelmholtzOp { int direction; double dt, nu; };
 int launch_lhs_diffusion(Sim *s, const double *p, double *out, const HelmholtzOp &op);

@@ -94,7 +94,8 @@ public:
   // host fields every step (12250-12495), so with obstacles the mode falls back to `across_steps`.
   bool device_led = false;
   bool dev_current = false;  // the device copies of vel and pres are newer than the host's
-  void invalidate() { host_vel_clean = host_pres_clean = false; dev_current = false; }
+  long chi_uploaded_step = -1;  // sim.step at which PressureProjectionHIP last sent chi up (ComputeForcesHIP reads it on the device)
+  void invalidate() { host_vel_clean = host_pres_clean = false; dev_current = false; chi_uploaded_step = -1; }
   void sync_host() {
     if (!dev_current) return;
     download(CUP3D_FIELD_VEL);
@@ -127,9 +128,23 @@ public:
     CUP3D_HIP_CALL(cup3d_sim_upload_block_list(dsim, field, (long)oslots.size(), oslots.data(), (const void *const *)ptrs.data()));
   }
 
+  // The global mesh object and the rank of every leaf, for the entry points that take them (cup3d_compute_forces_over_ranks).  Only a
+  // mirror with keep_global_mesh set (install() with CUP3D_HIP_FORCES=1) holds on to what ensure() gathered for the rank view; every
+  // other mirror frees it there, as before, and gathers it here on first use -- as does a uniform grid still in GridMPI's initial
+  // partition, for which ensure() gathers nothing.  COLLECTIVE when it gathers: every rank must ask.
+  bool keep_global_mesh = false;
+  void global_mesh(const cup3d_grid_t **mesh, const int32_t **owner) {
+    ensure();
+    if (!gmesh) gather_mesh();
+    *mesh = gmesh;
+    *owner = gowner.data();
+  }
+
 private:
   SimulationData &sim;
   cup3d_grid_t *grid = nullptr;
+  cup3d_grid_t *gmesh = nullptr;
+  std::vector<int32_t> gowner;
   cup3d_sim_t *dsim = nullptr;
   std::vector<long long> signature;  // (level, Z) of every local block the mirror was built for
   std::vector<void *> ptrs;
@@ -162,8 +177,42 @@ private:
   void release() {
     if (dsim) cup3d_sim_destroy(dsim);
     if (grid) cup3d_grid_destroy(grid);
+    if (gmesh) cup3d_grid_destroy(gmesh);
     dsim = nullptr;
     grid = nullptr;
+    gmesh = nullptr;
+    gowner.clear();
+  }
+  // every rank assembles the global leaf list with its owners -- the information the reference keeps in Grid::Octree on every rank
+  // (815-855) -- as a mesh object (gmesh) and the owner of each of its leaves (gowner)
+  void gather_mesh() {
+    const std::vector<Info> &I = sim.velInfo();
+    int rank = 0, size = 1;
+    MPI_Comm_rank(sim.comm, &rank);
+    MPI_Comm_size(sim.comm, &size);
+    const int bpd[3] = {sim.bpdx, sim.bpdy, sim.bpdz};
+    const int bc[3] = {(int)sim.BCx_flag, (int)sim.BCy_flag, (int)sim.BCz_flag};
+    int nloc = (int)I.size();
+    std::vector<int> counts(size), displs(size);
+    MPI_Allgather(&nloc, 1, MPI_INT, counts.data(), 1, MPI_INT, sim.comm);
+    long total = 0;
+    for (int r = 0; r < size; ++r) { displs[r] = (int)(2 * total); total += counts[r]; counts[r] *= 2; }
+    std::vector<long long> mine(2 * (size_t)nloc), all(2 * (size_t)total);
+    for (int i = 0; i < nloc; ++i) { mine[2 * i] = I[i].level; mine[2 * i + 1] = I[i].Z; }
+    MPI_Allgatherv(mine.data(), 2 * nloc, MPI_LONG_LONG, all.data(), counts.data(), displs.data(), MPI_LONG_LONG, sim.comm);
+    std::vector<int32_t> lv((size_t)total), own_in((size_t)total);
+    std::vector<int64_t> zs((size_t)total);
+    for (int r = 0, k = 0; r < size; ++r)
+      for (int i = 0; i < counts[r] / 2; ++i, ++k) { lv[k] = (int32_t)all[2 * k]; zs[k] = all[2 * k + 1]; own_in[k] = r; }
+    CUP3D_HIP_CALL(cup3d_grid_create_mesh(bpd, sim.levelMax, sim.maxextent, bc, total, lv.data(), zs.data(), &gmesh));
+    // the mesh object orders the leaves by blockID_2: owners follow through (level, Z)
+    std::vector<long long> tab(6 * (size_t)total);
+    std::vector<double> geom(4 * (size_t)total);
+    CUP3D_HIP_CALL(cup3d_grid_tables(gmesh, tab.data(), geom.data()));
+    std::map<std::pair<long long, long long>, int32_t> owner_of;
+    for (long k = 0; k < total; ++k) owner_of[{lv[k], zs[k]}] = own_in[k];
+    gowner.resize((size_t)total);
+    for (long k = 0; k < total; ++k) gowner[k] = owner_of[{tab[6 * k], tab[6 * k + 1]}];
   }
   void ensure() {
     const std::vector<Info> &I = sim.velInfo();
@@ -231,33 +280,16 @@ private:
       CUP3D_HIP_CALL(cup3d_grid_create_mesh(bpd, sim.levelMax, sim.maxextent, bc, (long)I.size(), lv.data(), zs.data(), &grid));
     } else if (not_uniform) {
       // (3) multi-level mesh (or a one-level mesh the LoadBalancer has re-dealt) spread over ranks: every rank assembles the global
-      // leaf list with its owners -- the information the reference keeps in Grid::Octree on every rank (815-855) -- and takes its view
-      // of it: ghost blocks + the two exchange plans (whole ghost blocks before a stencil kernel, face fluxes after a corrected one;
+      // leaf list with its owners (gather_mesh) and takes its view of it: ghost blocks + the two exchange plans (whole ghost blocks
+      // before a stencil kernel, face fluxes after a corrected one;
       // what SynchronizerMPI_AMR::_Setup 1979-2286 and FluxCorrectionMPI::prepare 2680-2824 derive from the octree)
-      int nloc = (int)I.size();
-      std::vector<int> counts(size), displs(size);
-      MPI_Allgather(&nloc, 1, MPI_INT, counts.data(), 1, MPI_INT, sim.comm);
-      long total = 0;
-      for (int r = 0; r < size; ++r) { displs[r] = (int)(2 * total); total += counts[r]; counts[r] *= 2; }
-      std::vector<long long> mine(2 * (size_t)nloc), all(2 * (size_t)total);
-      for (int i = 0; i < nloc; ++i) { mine[2 * i] = I[i].level; mine[2 * i + 1] = I[i].Z; }
-      MPI_Allgatherv(mine.data(), 2 * nloc, MPI_LONG_LONG, all.data(), counts.data(), displs.data(), MPI_LONG_LONG, sim.comm);
-      std::vector<int32_t> lv((size_t)total), own_in((size_t)total);
-      std::vector<int64_t> zs((size_t)total);
-      for (int r = 0, k = 0; r < size; ++r)
-        for (int i = 0; i < counts[r] / 2; ++i, ++k) { lv[k] = (int32_t)all[2 * k]; zs[k] = all[2 * k + 1]; own_in[k] = r; }
-      cup3d_grid_t *mesh = nullptr;
-      CUP3D_HIP_CALL(cup3d_grid_create_mesh(bpd, sim.levelMax, sim.maxextent, bc, total, lv.data(), zs.data(), &mesh));
-      // the mesh object orders the leaves by blockID_2: owners follow through (level, Z)
-      std::vector<long long> tab(6 * (size_t)total);
-      std::vector<double> geom(4 * (size_t)total);
-      CUP3D_HIP_CALL(cup3d_grid_tables(mesh, tab.data(), geom.data()));
-      std::map<std::pair<long long, long long>, int32_t> owner_of;
-      for (long k = 0; k < total; ++k) owner_of[{lv[k], zs[k]}] = own_in[k];
-      std::vector<int32_t> owner((size_t)total);
-      for (long k = 0; k < total; ++k) owner[k] = owner_of[{tab[6 * k], tab[6 * k + 1]}];
-      CUP3D_HIP_CALL(cup3d_grid_rank_view(mesh, owner.data(), rank, size, &grid));
-      cup3d_grid_destroy(mesh);
+      gather_mesh();
+      CUP3D_HIP_CALL(cup3d_grid_rank_view(gmesh, gowner.data(), rank, size, &grid));
+      if (!keep_global_mesh) {  // nobody will ask for them: one int32 per leaf of the whole mesh and the mesh object go back
+        cup3d_grid_destroy(gmesh);
+        gmesh = nullptr;
+        std::vector<int32_t>().swap(gowner);
+      }
     }
     if (!matches(grid)) {
       fprintf(stderr, "cup3d_hip: device topology differs from the host grid (blocks %ld vs %zu)\n", cup3d_grid_nblocks(grid), I.size());
@@ -413,6 +445,7 @@ public:
       kernelUpdateTmpV(sim);
       dev.upload(CUP3D_FIELD_TMPV);
       dev.upload(CUP3D_FIELD_CHI);
+      dev.chi_uploaded_step = sim.step;
       had_obstacles = true;
     } else if (had_obstacles) {
       CUP3D_HIP_CALL(cup3d_sim_fill(dev.handle(), CUP3D_FIELD_CHI, 0.0));
@@ -441,6 +474,113 @@ public:
   }
 };
 
+// ComputeForces::operator()(dt), main.cpp:12496-12503, with KernelComputeForces (12250-12494) on the device: the [-4,5) tiles of vel and
+// chi around the blocks an obstacle's surface touches are built there and only the 19 per-point arrays and the 19 sums of each such
+// block come back.  Installed only with CUP3D_HIP_FORCES=1 (install()).
+class ComputeForcesHIP : public Operator {
+  std::shared_ptr<DeviceMirror> devp;
+  DeviceMirror &dev;
+
+  static constexpr int nQoI = 19;
+  // the nineteen members in ObstacleBlock::sumQoI order (7289-7307)
+  static void qoi_members(ObstacleBlock &o, Real *q[nQoI]) {
+    Real *m[nQoI] = {&o.forcex,   &o.forcey,   &o.forcez,   &o.forcex_P, &o.forcey_P, &o.forcez_P,    &o.forcex_V, &o.forcey_V,    &o.forcez_V, &o.torquex,
+                     &o.torquey,  &o.torquez,  &o.drag,     &o.thrust,   &o.Pout,     &o.PoutBnd,     &o.defPower, &o.defPowerBnd, &o.pLocom};
+    for (int k = 0; k < nQoI; ++k) q[k] = m[k];
+  }
+  // the nineteen per-point arrays in the order of cup3d_obstacle_surface::points
+  static void point_arrays(ObstacleBlock &o, Real *a[nQoI]) {
+    Real *m[nQoI] = {o.pX, o.pY, o.pZ, o.P, o.fX, o.fY, o.fZ, o.fxV, o.fyV, o.fzV, o.omegaX, o.omegaY, o.omegaZ, o.vxDef, o.vX, o.vyDef, o.vY, o.vzDef, o.vZ};
+    for (int k = 0; k < nQoI; ++k) a[k] = m[k];
+  }
+
+public:
+  ComputeForcesHIP(SimulationData &s, std::shared_ptr<DeviceMirror> d) : Operator(s), devp(d), dev(*d) {}
+  void operator()(const Real dt) override {
+    (void)dt;
+    if (sim.obstacle_vector->nObstacles() == 0) return;  // 12497-12498
+    static_assert(sizeof(Real) == sizeof(double), "the device operators are FP64");
+    dev.handle();
+    // the functor reads vel, chi and pres: whatever the device does not hold in its current state goes up first.  host_vel_clean /
+    // host_pres_clean ("host copy == device copy") are trusted here in EVERY mode, not only under across_steps as the other operators
+    // do: directly behind PressureProjectionHIP in the pipeline (15243-15244), which has just downloaded both, that is right.  It is the
+    // across_steps contract all the same: a host that writes vel or pres and then calls this operator on its own must call
+    // DeviceMirror::invalidate() first, or the device evaluates the fields it still holds.
+    if (!(dev.dev_current || dev.host_vel_clean)) dev.upload(CUP3D_FIELD_VEL);
+    if (!(dev.dev_current || dev.host_pres_clean)) dev.upload(CUP3D_FIELD_PRES);
+    if (dev.chi_uploaded_step != sim.step) { dev.upload(CUP3D_FIELD_CHI); dev.chi_uploaded_step = sim.step; }
+    const std::vector<Info> &I = sim.velInfo();
+    const auto &obstacles = sim.obstacle_vector->getObstacleVector();
+    const size_t nobst = obstacles.size();
+    struct Packed {
+      std::vector<ObstacleBlock *> blocks;
+      std::vector<int32_t> slots, first, ijk;
+      std::vector<double> dchi, udef, points, qoi;
+    };
+    std::vector<Packed> packed(nobst);
+    std::vector<cup3d_obstacle_surface> surf(nobst);
+    for (size_t k = 0; k < nobst; ++k) {
+      Packed &P = packed[k];
+      const std::vector<ObstacleBlock *> &ob = obstacles[k]->getObstacleBlocks();
+      P.first.push_back(0);
+      for (size_t i = 0; i < I.size(); ++i) {  // block slot i of the mirror is m_vInfo entry i
+        ObstacleBlock *o = ob[I[i].blockID];
+        if (o == nullptr || o->nPoints == 0) continue;  // 12278-12281
+        P.blocks.push_back(o);
+        P.slots.push_back((int32_t)i);
+        for (int p = 0; p < o->nPoints; ++p) {
+          const surface_data *sd = o->surface[p];
+          P.ijk.insert(P.ijk.end(), {(int32_t)sd->ix, (int32_t)sd->iy, (int32_t)sd->iz});
+          P.dchi.insert(P.dchi.end(), {(double)sd->dchidx, (double)sd->dchidy, (double)sd->dchidz});
+        }
+        P.first.push_back((int32_t)(P.ijk.size() / 3));
+        const double *u = &o->udef[0][0][0][0];
+        P.udef.insert(P.udef.end(), u, u + 8 * 8 * 8 * 3);
+        Real *q[nQoI];
+        qoi_members(*o, q);
+        for (int m = 0; m < nQoI; ++m) P.qoi.push_back(*q[m]);  // eight of them carry on (12283-12293)
+      }
+      P.points.resize((size_t)nQoI * (P.ijk.size() / 3));
+      cup3d_obstacle_surface &S = surf[k];
+      S.nblocks = (long)P.slots.size();
+      S.slots = P.slots.data();
+      S.first = P.first.data();
+      S.ijk = P.ijk.data();
+      S.dchi = P.dchi.data();
+      S.udef = P.udef.data();
+      const std::array<Real, 3> cm = obstacles[k]->getCenterOfMass(), ut = obstacles[k]->getTranslationVelocity(), om = obstacles[k]->getAngularVelocity();
+      for (int d = 0; d < 3; ++d) { S.cm[d] = cm[d]; S.vel[d] = ut[d]; S.omega[d] = om[d]; }
+      S.points = P.points.data();
+      S.qoi = P.qoi.data();
+    }
+    int size = 1;
+    MPI_Comm_size(sim.comm, &size);
+    if (size > 1) {
+      const cup3d_grid_t *mesh = nullptr;
+      const int32_t *owner = nullptr;
+      dev.global_mesh(&mesh, &owner);
+      CUP3D_HIP_CALL(cup3d_compute_forces_over_ranks(dev.handle(), mesh, owner, sim.nu, (int)nobst, surf.data()));
+    } else {
+      CUP3D_HIP_CALL(cup3d_compute_forces(dev.handle(), sim.nu, (int)nobst, surf.data()));
+    }
+    for (size_t k = 0; k < nobst; ++k) {
+      Packed &P = packed[k];
+      const size_t np = P.ijk.size() / 3;
+      for (size_t b = 0; b < P.blocks.size(); ++b) {
+        ObstacleBlock &o = *P.blocks[b];
+        Real *a[nQoI], *q[nQoI];
+        point_arrays(o, a);
+        qoi_members(o, q);
+        for (int m = 0; m < nQoI; ++m) {
+          for (int p = 0; p < o.nPoints; ++p) a[m][p] = P.points[(size_t)m * np + P.first[b] + p];
+          *q[m] = P.qoi[b * nQoI + m];
+        }
+      }
+    }
+    sim.obstacle_vector->computeForces();  // 12502: the sums over blocks and ranks (MPI_Allreduce, 13087) stay the host's
+  }
+};
+
 // One DeviceMirror per SimulationData, shared by every HIP-backed operator / solver built for it.
 inline std::shared_ptr<DeviceMirror> mirror_of(SimulationData &sim) {
   static std::map<SimulationData *, std::weak_ptr<DeviceMirror>> reg;
@@ -463,6 +603,7 @@ struct Installed {
   std::shared_ptr<ExternalForcingHIP> forcing;
   std::shared_ptr<UpdateObstaclesHIP> update_obstacles;
   std::shared_ptr<PressureProjectionHIP> projection;
+  std::shared_ptr<ComputeForcesHIP> forces;  // only with CUP3D_HIP_FORCES=1
 };
 
 // Swap the hot-path operators of an initialised Simulation for the HIP-backed ones.
@@ -473,6 +614,8 @@ struct Installed {
 // velocity only in the blocks an obstacle covers, so those blocks alone make the round trip (UpdateObstaclesHIP fetches them,
 // PressureProjectionHIP sends them back); without obstacles both return immediately (13813-13814, 14327-14328).  With
 // FixMassFlux in between, every operator round-trips in full as before.
+// CUP3D_HIP_FORCES=1 (environment): ComputeForces (15244) is replaced by ComputeForcesHIP as well; without it that entry of the
+// pipeline stays the reference's own.
 inline Installed install(SimulationData &sim, int resident = -1) {
   Installed r;
   r.mirror = mirror_of(sim);
@@ -491,8 +634,14 @@ inline Installed install(SimulationData &sim, int resident = -1) {
   r.mirror->resident = resident != 0 && safe;
   r.mirror->across_steps = resident >= 2 && safe;
   r.mirror->device_led = resident >= 3 && safe;
+  const char *forces_env = getenv("CUP3D_HIP_FORCES");
+  const bool forces = forces_env && atoi(forces_env) == 1;
+  if (forces) r.mirror->keep_global_mesh = true;
   for (auto &op : sim.pipeline) {
-    if (std::dynamic_pointer_cast<AdvectionDiffusion>(op)) {
+    if (forces && std::dynamic_pointer_cast<ComputeForces>(op)) {
+      r.forces = std::make_shared<ComputeForcesHIP>(sim, r.mirror);
+      op = r.forces;
+    } else if (std::dynamic_pointer_cast<AdvectionDiffusion>(op)) {
       r.advdiff = std::make_shared<AdvectionDiffusionHIP>(sim, r.mirror);
       op = r.advdiff;
     } else if (std::dynamic_pointer_cast<AdvectionDiffusionImplicit>(op)) {  // setupOperators 15231-15232

@@ -232,6 +232,7 @@ class SimulationData:
         self.last_poisson = None
         self.Rtol, self.Ctol, self.levelMaxVorticity = 1e9, 0.0, levelMax   # -Rtol / -Ctol / -levelMaxVorticity (15340-15342)
         self.obstacles = []            # ObstacleData list (geometry and motion come from the host)
+        self.surfaces = []             # ObstacleSurface list: what ComputeForces evaluates
         self.lambda_penal = 1e6        # sim.lambda (-lambda)
         self.bImplicitPenalization = True
 
@@ -515,6 +516,55 @@ class Penalization(Operator):
         check(lib().cup3d_penalization(s.handle, dt, s.lambda_penal, 1 if s.bImplicitPenalization else 0, len(s.obstacles), arr))
         for o, a in zip(s.obstacles, arr):
             o.force, o.torque = np.array(a.force[:]), np.array(a.torque[:])
+
+
+class ObstacleSurface:
+    """Host-side description of one obstacle's surface for ComputeForces: the ObstacleBlocks that have surface points (block slots, udef in
+    the reference's layout), their surface_data as a CSR list -- block i owns points [first[i], first[i+1]), ijk = ix, iy, iz, dchi =
+    dchidx, dchidy, dchidz -- the rigid motion, and qoi [n][19], the blocks' nineteen sums (ObstacleBlock::sumQoI order, main.cpp:7289-7307)
+    as they stand before the call: eight of them carry on (12283-12293).  Empty lists: this rank holds none of the obstacle's blocks."""
+
+    def __init__(self, slots, first, ijk, dchi, udef, cm, vel, omega, qoi=None):
+        self.slots = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        n = len(self.slots)
+        self.first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1) if n else np.zeros(1, dtype=np.int32)
+        self.ijk = np.ascontiguousarray(ijk, dtype=np.int32).reshape(-1, 3)
+        self.dchi = np.ascontiguousarray(dchi, dtype=np.float64).reshape(-1, 3)
+        self.udef = np.ascontiguousarray(udef, dtype=np.float64).reshape(n, 8, 8, 8, 3)
+        self.cm, self.vel, self.omega = (np.array(v, dtype=np.float64) for v in (cm, vel, omega))
+        self.qoi = np.zeros((n, 19)) if qoi is None else np.array(qoi, dtype=np.float64).reshape(n, 19)
+        if len(self.first) != n + 1 or len(self.ijk) != len(self.dchi):
+            raise ValueError("ObstacleSurface: first needs one entry per block plus one, ijk and dchi one row per point")
+
+
+class ComputeForces(Operator):
+    """ComputeForces::operator()(dt) without Obstacle::computeForces (main.cpp:12496-12503): KernelComputeForces on the device for
+    sim.surfaces (ObstacleSurface list) from the resident vel, chi and pres.  Returns [(points [19][npoints], qoi [n][19])] per obstacle
+    -- the 19 per-point arrays in the order pX pY pZ P fX fY fZ fxV fyV fzV omegaX omegaY omegaZ vxDef vX vyDef vY vzDef vZ and the
+    blocks' sums -- and leaves qoi in the ObstacleSurface, where the next call starts from."""
+
+    def __call__(self, dt=0, mesh=None, owner=None):
+        """mesh / owner (the global mesh object and the rank of every leaf): the mesh is spread over ranks and this is a collective."""
+        s = self.sim
+        surfaces = getattr(s, "surfaces", [])
+        arr = (capi.ObstacleSurface * max(1, len(surfaces)))()
+        out = []
+        for o, a in zip(surfaces, arr):
+            points, qoi = np.zeros((19, len(o.ijk))), o.qoi.copy()
+            a.nblocks = len(o.slots)
+            a.slots, a.first, a.ijk, a.dchi, a.udef = (v.ctypes.data for v in (o.slots, o.first, o.ijk, o.dchi, o.udef))
+            a.points, a.qoi = points.ctypes.data, qoi.ctypes.data
+            for d in range(3):
+                a.cm[d], a.vel[d], a.omega[d] = o.cm[d], o.vel[d], o.omega[d]
+            out.append((points, qoi))
+        if mesh is None:
+            check(lib().cup3d_compute_forces(s.handle, float(s.nu), len(surfaces), arr))
+        else:
+            ow = np.ascontiguousarray(owner, dtype=np.int32)
+            check(lib().cup3d_compute_forces_over_ranks(s.handle, mesh.handle, ow.ctypes.data_as(C.c_void_p), float(s.nu), len(surfaces), arr))
+        for o, (_, qoi) in zip(surfaces, out):
+            o.qoi = qoi
+        return out
 
 
 class ExternalForcing(Operator):

@@ -350,6 +350,48 @@ CUP3D_API int cup3d_penalization(cup3d_sim_t *, double dt, double lambda, int im
 /* kernelUpdateTmpV (14948-14979): tmpV += udef where chi <= the obstacle's chi; call after clearing tmpV and before
  * cup3d_pressure_rhs / cup3d_pressure_project (15066-15085) */
 CUP3D_API int cup3d_update_tmpv(cup3d_sim_t *, int nobstacles, const cup3d_obstacle *obstacles);
+/* ComputeForces::operator() without Obstacle::computeForces (main.cpp:12496-12503): KernelComputeForces::visit (12273-12493) on the
+ * device.  One cup3d_obstacle_surface = the ObstacleBlocks of one Obstacle on this rank that have surface points (nPoints > 0; 12280
+ * skips the others) with their surface_data as a CSR list: block i owns points [first[i], first[i+1]), ijk = surface_data::ix, iy, iz,
+ * dchi = surface_data::dchidx, dchidy, dchidz.  Per point: the unit normal, the 5-step march along it (12323-12341), one-sided first
+ * derivatives of vel with their 6-, 3- and 2-point branches, second and mixed derivatives, the Taylor shift back to the surface cell
+ * (12420-12437) and everything from 12438 to 12491, in the reference's association -- including, as written there, the `sx` of the
+ * 2-point dveldy branch (12364) and the precedence of the mixed fallback, sx*sy*(a-b) - (c-d) (12394-12395, 12406-12407, 12418-12419).
+ * points: the 19 arrays the functor writes, [19][npoints] in the order pX pY pZ P fX fY fZ fxV fyV fzV omegaX omegaY omegaZ vxDef vX
+ * vyDef vY vzDef vZ (it never writes fxP / fyP / fzP).  qoi: per block the 19 sums in ObstacleBlock::sumQoI order (7289-7307), points
+ * added in order i = 0..nPoints-1 as the reference adds them, bit for bit.  IN/OUT: visit() zeroes eleven of them at entry (12283-12293:
+ * forcex, forcex_V, forcex_P, torquex/y/z, thrust, drag, Pout, defPower, pLocom); forcey, forcez, forcey_P, forcez_P, forcey_V, forcez_V,
+ * PoutBnd and defPowerBnd go on from the value passed in. */
+typedef struct {
+  long nblocks;            /* ObstacleBlocks of this obstacle with nPoints > 0 on this rank */
+  const int32_t *slots;    /* [nblocks] */
+  const int32_t *first;    /* [nblocks+1] */
+  const int32_t *ijk;      /* [npoints][3] */
+  const double *dchi;      /* [npoints][3] */
+  const double *udef;      /* [nblocks][8][8][8][3] */
+  double cm[3], vel[3], omega[3];
+  double *points;          /* out [19][npoints], order above */
+  double *qoi;             /* in/out [nblocks][19], sumQoI order */
+} cup3d_obstacle_surface;
+/* Obstacles one after another (12270-12271).  Per obstacle the [-4,5) tensorial tiles of vel and chi of `slots` are built by the kernel
+ * of cup3d_sim_labs_device into a grow-only scratch buffer of the sim (counted in cup3d_sim_device_bytes; at most 512 blocks' tiles,
+ * 64 MiB, at a time: longer lists go through it chunk by chunk), pres is read from the resident field, and points and qoi come back
+ * with one download each (counted in cup3d_run_stats.field_bytes_downloaded): 19 doubles per point and per block cross PCIe instead of
+ * the 131 072 B per block the tiles would.  vel, chi and pres are only read.  nblocks = 0 and nobstacles = 0 are no-ops.
+ * CUP3D_EINVAL, nothing touched: a null array with nblocks > 0, a slot outside [0, nblocks of the sim), first not non-decreasing from 0,
+ * an ijk outside [0, 8), a sim on a rank view or on one rank's share of a uniform grid. */
+CUP3D_API int cup3d_compute_forces(cup3d_sim_t *, double nu, int nobstacles, cup3d_obstacle_surface *obstacles);
+/* The same on a mesh spread over ranks (mesh / owner as for cup3d_sim_labs_over_ranks, whose device variant supplies the tiles).
+ * COLLECTIVE: every rank calls it with the same nobstacles; a rank that holds none of an obstacle's blocks passes nblocks = 0.  Every
+ * rank makes the same number of tile calls per obstacle -- the largest block count of a rank, read off `owner`, cut into chunks of 4096
+ * blocks (a scratch of at most 512 MiB, allocated only as far as the rank's share of the obstacle needs it) -- so an obstacle may list
+ * at most as many blocks as the rank holds.  COST: that number does not shrink with the obstacle.  A rank of up to 4096 blocks makes one
+ * round, i.e. two calls of cup3d_sim_labs_over_ranks_device, per obstacle; 512^3 on 8 ranks (32 768 blocks per rank) makes 8 rounds, and a
+ * round in which no rank asks for a tile still agrees and exchanges an empty request.  It adds no collective of its own: the sum of the 19 values over blocks
+ * and ranks stays the host's (Obstacle::computeForces, MPI_Allreduce at 13087).  A rank whose own arguments are refused still takes
+ * part in the tile calls, asking for nothing, and then returns CUP3D_EINVAL with nothing touched; the other ranks finish. */
+CUP3D_API int cup3d_compute_forces_over_ranks(cup3d_sim_t *, const cup3d_grid_t *mesh, const int32_t *owner, double nu, int nobstacles,
+                                              cup3d_obstacle_surface *obstacles);
 /* Implicit diffusion: AdvectionDiffusionImplicit (main.cpp:7148-7157, 10030-10119), selected by -implicitDiffusion (15231-15232).
  * One call = euler(dt): KernelAdvect, the explicit-diffusion guess, KernelDiffusionRHS and one DiffusionSolver::solve per velocity
  * component.  `params`: tol / tol_rel = sim.DiffusionErrorTol / DiffusionErrorTolRel (15369-15370), max_iter; mean_constraint,

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <memory>
 #include <stdexcept>
+#include <utility>
 
 #include "sim.hpp"
 #include "tile.hpp"
@@ -87,8 +88,8 @@ __device__ __forceinline__ double interp1d(const double *__restrict__ P0, int p,
 // CoarseFineInterpolation, finite-difference mode (main.cpp:4419-4600): the coarse-side value `av` of a fine ghost cell -- the two 1-D
 // quadratic interpolations along the face's tangential axes plus the mixed term -- from the coarse layer behind the face.  P0 = the coarse
 // cell that holds the ghost cell, (p1, p2) its tangential position (0..3), st1 / st2 the strides of the layer along the two axes, bit1 /
-// bit2 which child of the coarse cell the ghost cell is.  ONE definition for the three callers (the ghost slabs of the star stencils,
-// k_ghost_prolong; the tensorial tiles of the mesh adaptation, k_refine and k_grad_chi): a bit-exactness fix lands once.
+// bit2 which child of the coarse cell the ghost cell is.  ONE definition for the two callers (the ghost slabs of the star stencils,
+// ghost_prolong_face; phase D of the ghosted tiles, labs_phases.hpp): a bit-exactness fix lands once.
 __device__ __forceinline__ double fd_mode_av(const double *__restrict__ P0, int p1, int p2, int st1, int st2, int bit1, int bit2) {
   const double dd1 = 0.25 * (2 * bit1 - 1), dd2 = 0.25 * (2 * bit2 - 1);
   const double *coef1 = dd1 > 0 ? kCoefPlus : kCoefMinus, *coef2 = dd2 > 0 ? kCoefPlus : kCoefMinus;
@@ -259,158 +260,111 @@ __global__ void __launch_bounds__(64) k_flux_fix_blocks(AmrDev a, const int32_t 
   }
 }
 
+// ==== Ghosted block tiles: BlockLab::load + post_load (main.cpp:3623-3787) for one block, ONE implementation for every consumer of a
+// tensorial (or star) tile: cup3d_sim_labs / cup3d_sim_labs_device (k_labs), cup3d_sim_labs_over_ranks (k_labs_view), the refinement
+// of mesh adaptation (k_refine, the [-1,2) tile) and GradChiOnTmp (k_grad_chi, the [-2,3) tile).  It uses the device helpers above --
+// avg_down8 / avg_block, fd_mode_av / fd_mode_blend (with interp1d), test_interp -- so a bit-exactness fix to the reference's ghost
+// rules lands once.  (k_ghosts above builds star slabs in another shape, for the solver's hot path, and stays on its own.)
+//
+// The stencil kernels build the three tile shapes they need in LDS and never hand them out; this is the general operation for a
+// consumer OUTSIDE the library (the kernel-functor protocol of compute<Lab>): block b with its ghosts for the box [-w, w+1)^3,
+// w = 1..4, star or tensorial, in the reference's Matrix3D layout [L][L][L][nc] (x fastest, component innermost, L = 8 + 2w).
+// One workgroup per tile, one component at a time in LDS (16^3 fine cells + the 10^3 coarse shadow tile = 40 768 B), in the
+// reference's order:
+//   A. interior copy, SameLevelExchange (3823-3876), FineToCoarseExchange = AverageDown of the finer leaves (3907-4065);
+//   B. the coarse shadow tile m_CoarsenedBlock: coarser leaves copied (CoarseFineExchange 4066-4170), same-level neighbours
+//      averaged down (FillCoarseVersion 4171-4235; every one of them -- the cells the UseCoarseStencil rule 3788-3822 would leave
+//      out are read by no interpolation: tests/test_gpu_labs.py::test_tiles_equal_the_reference, the reference's own tiles on four
+//      meshes, is the test that a violation would turn red), the block's own average-down (post_load 3750-3778);
+//   C. _apply_bc on the coarse tile (3781): ordered passes x, y, z, each over the whole ghost slab;
+//   D. CoarseFineInterpolation (4236-4614): TestInterp everywhere behind a coarser neighbour, then the finite-difference mode with
+//      the 1/15 blend on the two layers next to a FACE (it overwrites TestInterp there, as in the reference);
+//   E. _apply_bc on the fine tile: ordered passes x, y, z, each over the whole ghost slab, transverse ghosts of earlier passes included;
+//   F. the cells the reference leaves undefined -- edge and corner ghosts of a star tile with w <= 2, where use_averages (3618-3621)
+//      does not hold -- leave as quiet NaN, so that a consumer that reads them sees it.
+// A tile with w >= 3 is built tensorially by the reference whatever the stencil says (use_averages), so `tensorial` only decides F.
+// The kernel reads blocks only: it neither needs nor touches the ghost slabs the stencil kernels keep behind kNbrHalo.
+struct LabDev {
+  const int32_t *n27;        // [nb][27]
+  const int32_t *index;      // [nb][3]
+  const int32_t *level;      // [nb]
+  const int32_t *finer_row;  // [nb]: row of `finer`, or -1
+  const int32_t *finer;      // [rows][27][8]
+  int bpd[3], bc[3];
+  int bc_comp;  // scalar fields: -1 = zero-gradient domain faces (ScalarLab); k = element of BlockLabBC<.., direction k>
+};
+
+constexpr int kLabCoarse = 10;  // coarse shadow tile: coarse cells [-3, 7)^3 (w = 4 reads [-3, 6])
+__device__ __forceinline__ int cix10(int X, int Y, int Z) { return ((Z + 3) * kLabCoarse + (Y + 3)) * kLabCoarse + (X + 3); }
+
+// domain-face rule of one tile value: the vector lab negates every component at a wall and the normal one at a freespace face
+// (6107-6503), the scalar lab copies (6561-6581), the scalar of BlockLabBC<.., direction k> behaves as component k of a vector
+__device__ __forceinline__ double lab_bc_value(double v, int nc, int c, int bc_comp, int bc_kind, int d) {
+  const int cc = nc == 3 ? c : bc_comp;
+  return (cc >= 0 && (bc_kind == CUP3D_BC_WALL || cc == d)) ? -v : v;
+}
+
+// The set-up (labs_setup.hpp) and phases A-E for one component (labs_phases.hpp) live once and are included as text into the four
+// kernels below, which differ in where the blocks of a tile's neighbourhood live and in what they do with the finished tile.  k_labs,
+// one rank: every slot is a row of the field array; phase F stores the tile.  k_labs_view, a mesh spread over ranks
+// (cup3d_sim_labs_over_ranks): slots [0, n_local) of the rank's tensorial view are rows of the sim's own field array, read in place; a
+// ghost slot is a row of the call's ghost pool, found through pool_of (-1: not fetched -- row 0 of the pool, which holds NaN, so that
+// a read the request plan did not foresee shows in the tile instead of leaving the buffer).  k_refine and k_grad_chi (mesh adaptation)
+// read rows of a field array, as k_labs does, and keep the tile in LDS for their operator.
+struct LabSrcView {
+  const double *__restrict__ field;
+  const double *__restrict__ pool;      // [1 + fetched ghosts][nc][512]
+  const int32_t *__restrict__ pool_of;  // [nghost]
+  int n_local;
+  __device__ __forceinline__ const double *blk(int slot, int nc, int c) const {
+    if (slot < n_local) return field + ((size_t)slot * nc + c) * 512;
+    return pool + ((size_t)(pool_of[slot - n_local] + 1) * nc + c) * 512;
+  }
+};
+
+#define LABS_BLOCK(slot, c) (src + ((size_t)(slot) * nc + (c)) * 512)
+#define LABS_CELL(slot, c, i) src[((size_t)(slot) * nc + (c)) * 512 + (i)]
+#define LABS_SLOT slots ? slots[blockIdx.x] : first + (int)blockIdx.x
+#define LABS_AFTER_SLOT double *__restrict__ tile = out + (size_t)blockIdx.x * L3 * nc;
+template <int W>
+__global__ void __launch_bounds__(256) k_labs(LabDev a, const int32_t *__restrict__ slots, int first, int star, const double *__restrict__ src, int nc,
+                                              double *__restrict__ out) {
+#include "labs_setup.hpp"
+  for (int c = 0; c < nc; ++c) {
+#include "labs_phases.hpp"
+    // F. the tile leaves in the reference's layout; what the reference leaves undefined leaves as NaN
+    for (int e = t; e < L3; e += 256) {
+      double v = lab[e];
+      if (W <= 2 && star) {
+        const int x = e % L - W, y = (e / L) % L - W, z = e / (L * L) - W;
+        if ((x < 0 || x > 7) + (y < 0 || y > 7) + (z < 0 || z > 7) > 1) v = __builtin_nan("");
+      }
+      tile[(size_t)e * nc + c] = v;
+    }
+    __syncthreads();
+  }
+}
+#undef LABS_SLOT
+#undef LABS_AFTER_SLOT
+
 // ---- mesh adaptation: the eight children of a refined block (refine_1 + RefineBlocks, main.cpp:5227-5249, 5493-5565).
 // One workgroup per refined parent builds the parent's tensorial [-1,2) tile on the OLD mesh in LDS exactly as BlockLab::load
-// does -- same-level neighbours copied, finer ones averaged down, coarser ones interpolated from the coarse shadow tile
-// (faces: finite-difference mode, edges and corners: TestInterp), domain faces last -- and expands it.
-struct RefineTab {
-  const int32_t *items;  // [n][9]: parent slot (old mesh), eight child slots (new mesh, child = I + 2J + 4K)
-  const int32_t *finer;  // [n][27][8]: old-mesh slot of the finer leaf behind code for the octant (bits of x,y,z >= 4), -1 unused
-};
-__device__ __forceinline__ int lix10(int x, int y, int z) { return ((z + 1) * 10 + (y + 1)) * 10 + (x + 1); }
-__device__ __forceinline__ int cix8(int X, int Y, int Z) { return ((Z + 2) * 8 + (Y + 2)) * 8 + (X + 2); }
-
+// does (phases A-E at W = 1; a scalar is never negated at a domain face: bc_comp = -1), one component at a time, and expands it.
+// items[n][9]: parent slot (old mesh), eight child slots (new mesh, child = I + 2J + 4K)
 template <int NC>
-__global__ void __launch_bounds__(256) k_refine(AmrDev a, RefineTab tab, const double *__restrict__ src, double *__restrict__ dst) {
-  __shared__ double lab[NC * 1000];
-  __shared__ double Ct[NC * 512];  // coarse shadow tile, coarse cells [-2,6)^3
-  const int it = blockIdx.x, t = threadIdx.x;
-  const int pb = tab.items[9 * it];
-  const int32_t *n27 = a.nbr27 + 27 * pb;
-  const int32_t *fin = tab.finer + (size_t)it * 27 * 8;
-  const int par[3] = {a.index[3 * pb] & 1, a.index[3 * pb + 1] & 1, a.index[3 * pb + 2] & 1};
-  bool has_coarse = false;
-  for (int i = 0; i < 27; ++i) has_coarse = has_coarse || n27[i] >= kNbrCoarser;
-  // A. centre, same-level neighbours (SameLevelExchange), finer neighbours (FineToCoarseExchange)
-  for (int e = t; e < 1000; e += 256) {
-    const int l[3] = {e % 10 - 1, (e / 10) % 10 - 1, e / 100 - 1};
-    int code[3], loc[3], fl[3], q = 0;
-    for (int d = 0; d < 3; ++d) {
-      code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
-      loc[d] = l[d] - 8 * code[d];
-      fl[d] = code[d] < 0 ? 6 : (code[d] > 0 ? 0 : (2 * l[d]) & 7);
-      if (code[d] == 0 && l[d] >= 4) q |= 1 << d;
-    }
-    const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
-    const int n = n27[icode];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      double v = 0.0;
-      if (n >= 0 && n < kNbrCoarser) v = src[((size_t)n * NC + c) * 512 + (loc[2] * 8 + loc[1]) * 8 + loc[0]];
-      else if (n == kNbrFiner) v = avg_block(src + ((size_t)fin[icode * 8 + q] * NC + c) * 512, fl[0], fl[1], fl[2]);
-      lab[c * 1000 + e] = v;
-    }
-  }
-  __syncthreads();
-  if (has_coarse) {
-    // B. coarse shadow tile: own block averaged down (post_load 3750-3778), coarser leaves copied (CoarseFineExchange),
-    //    same-level neighbours averaged down (FillCoarseVersion)
-    for (int e = t; e < 512; e += 256) {
-      const int P[3] = {e % 8 - 2, (e / 8) % 8 - 2, e / 64 - 2};
-      int code[3];
-      for (int d = 0; d < 3; ++d) code[d] = P[d] < 0 ? -1 : (P[d] > 3 ? 1 : 0);
-      const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
-      const int n = n27[icode];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        double v = 0.0;
-        if (icode == 13) {
-          const double *L = lab + c * 1000;
-          double w[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) w[q] = L[lix10(2 * P[0] + (q & 1), 2 * P[1] + ((q >> 1) & 1), 2 * P[2] + (q >> 2))];  // x fastest here
-          v = avg_down8(w);
-        } else if (n >= kNbrCoarser) {
-          v = src[((size_t)(n - kNbrCoarser) * NC + c) * 512 + ((par[2] * 4 + P[2] + 8) & 7) * 64 + ((par[1] * 4 + P[1] + 8) & 7) * 8 + ((par[0] * 4 + P[0] + 8) & 7)];
-        } else if (n >= 0) {
-          v = avg_block(src + ((size_t)n * NC + c) * 512, 2 * P[0] - 8 * code[0], 2 * P[1] - 8 * code[1], 2 * P[2] - 8 * code[2]);
-        }
-        Ct[c * 512 + e] = v;
-      }
-    }
-    __syncthreads();
-    // C. domain faces on the coarse tile (_apply_bc(info, t, true), 3781): both ghost layers behind the face, every
-    //    transverse position, from the face cell; order x-,x+,y-,y+,z-,z+
-    for (int f = 0; f < 6; ++f) {
-      const int n = a.nbr[pb * 6 + f];
-      if (n >= 0) continue;
-      const int d = f >> 1, side = f & 1, d1 = (d + 1) % 3, d2 = (d + 2) % 3;
-      if (t < 128) {
-        int p[3], q[3];
-        p[d] = side ? 4 + (t >> 6) : -1 - (t >> 6);
-        q[d] = side ? 3 : 0;
-        p[d1] = q[d1] = (t & 7) - 2;
-        p[d2] = q[d2] = ((t >> 3) & 7) - 2;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          double v = Ct[c * 512 + cix8(q[0], q[1], q[2])];
-          if (NC == 3 && (n == -3 || c == d)) v = -v;
-          Ct[c * 512 + cix8(p[0], p[1], p[2])] = v;
-        }
-      }
-      __syncthreads();
-    }
-    // D. CoarseFineInterpolation (4236-4614) of the ghosts behind coarser neighbours
-    for (int e = t; e < 1000; e += 256) {
-      const int l[3] = {e % 10 - 1, (e / 10) % 10 - 1, e / 100 - 1};
-      int code[3], X[3], bit[3], ncode = 0;
-      for (int d = 0; d < 3; ++d) {
-        code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
-        ncode += code[d] != 0;
-        X[d] = code[d] < 0 ? -1 : (code[d] > 0 ? 4 : l[d] >> 1);
-        bit[d] = code[d] < 0 ? 1 : (code[d] > 0 ? 0 : l[d] & 1);
-      }
-      if (ncode == 0 || n27[(code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1)] < kNbrCoarser) continue;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const double *C0 = Ct + c * 512;
-        double v;
-        if (ncode == 1) {  // face: finite-difference mode
-          const int ax = code[0] ? 0 : (code[1] ? 1 : 2), ax1 = ax == 0 ? 1 : 0, ax2 = ax == 2 ? 1 : 2;
-          const int st1 = ax1 == 0 ? 1 : 8, st2 = ax2 == 1 ? 8 : 64;
-          const int p1 = X[ax1], p2 = X[ax2];
-          const double av = fd_mode_av(C0 + cix8(X[0], X[1], X[2]), p1, p2, st1, st2, bit[ax1], bit[ax2]);
-          int cb[3] = {l[0], l[1], l[2]}, cc[3] = {l[0], l[1], l[2]};
-          cb[ax] = code[ax] > 0 ? 7 : 0;
-          cc[ax] = code[ax] > 0 ? 6 : 1;
-          const double bv = lab[c * 1000 + lix10(cb[0], cb[1], cb[2])], cv = lab[c * 1000 + lix10(cc[0], cc[1], cc[2])];
-          v = fd_mode_blend(av, bv, cv, 0);
-        } else {  // edge / corner: TestInterp
-          v = test_interp([&](int i, int j, int k) -> double { return C0[cix8(X[0] - 1 + i, X[1] - 1 + j, X[2] - 1 + k)]; }, bit);
-        }
-        lab[c * 1000 + e] = v;
-      }
-    }
-    __syncthreads();
-  }
-  // E. domain faces on the fine tile, order x-,x+,y-,y+,z-,z+ (as k_prolong)
-  for (int f = 0; f < 6; ++f) {
-    const int n = a.nbr[pb * 6 + f];
-    if (n >= 0) continue;
-    const int d = f >> 1, side = f & 1, ghost = side ? 8 : -1, face = side ? 7 : 0, d1 = (d + 1) % 3, d2 = (d + 2) % 3;
-    if (t < 100) {
-      int p[3], q[3];
-      p[d] = ghost; q[d] = face;
-      p[d1] = q[d1] = t % 10 - 1;
-      p[d2] = q[d2] = t / 10 - 1;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        double v = lab[c * 1000 + lix10(q[0], q[1], q[2])];
-        if (NC == 3 && (n == -3 || c == d)) v = -v;
-        lab[c * 1000 + lix10(p[0], p[1], p[2])] = v;
-      }
-    }
-    __syncthreads();
-  }
-  // F. RefineBlocks, 5493-5565
-  for (int k = 0; k < 2; ++k) {
-    const int cell = k * 256 + t, x = cell & 7, y = (cell >> 3) & 7, z = cell >> 6;
-    const int fs = tab.items[9 * it + 1 + (z >> 2) * 4 + (y >> 2) * 2 + (x >> 2)];
-    const int i = 2 * (x & 3), j = 2 * (y & 3), kk = 2 * (z & 3);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const double *L = lab + c * 1000;
-#define Lb(a_, b_, c_) L[lix10(x + (a_), y + (b_), z + (c_))]
+__global__ void __launch_bounds__(256) k_refine(LabDev a, const int32_t *__restrict__ items, const double *__restrict__ src, double *__restrict__ dst) {
+  constexpr int W = 1, nc = NC;
+#define LABS_SLOT items[9 * blockIdx.x]
+#include "labs_setup.hpp"
+#undef LABS_SLOT
+  for (int c = 0; c < nc; ++c) {
+#include "labs_phases.hpp"
+    // RefineBlocks, 5493-5565
+    for (int k = 0; k < 2; ++k) {
+      const int cell = k * 256 + t, x = cell & 7, y = (cell >> 3) & 7, z = cell >> 6;
+      const int fs = items[9 * blockIdx.x + 1 + (z >> 2) * 4 + (y >> 2) * 2 + (x >> 2)];
+      const int i = 2 * (x & 3), j = 2 * (y & 3), kk = 2 * (z & 3);
+#define Lb(a_, b_, c_) lab[lix(x + (a_), y + (b_), z + (c_))]
       const double dudx = 0.5 * (Lb(1, 0, 0) - Lb(-1, 0, 0));
       const double dudy = 0.5 * (Lb(0, 1, 0) - Lb(0, -1, 0));
       const double dudz = 0.5 * (Lb(0, 0, 1) - Lb(0, 0, -1));
@@ -434,136 +388,30 @@ __global__ void __launch_bounds__(256) k_refine(AmrDev a, RefineTab tab, const d
       B(1, 1, 1) = u + 0.25 * (dudx + dudy + dudz) + q2 + 0.0625 * (dudxdy + dudxdz + dudydz);
 #undef B
     }
+    __syncthreads();  // the next component reuses lab[]
   }
 }
 
 // ---- compute<ScalarLab>(GradChiOnTmp(sim), sim.chi), main.cpp:8540-8600: the chi-driven half of adaptMesh's tagging input.
-// One workgroup per block builds the TENSORIAL [-2,3) tile of chi exactly as BlockLab::load does for that stencil -- same-level
-// neighbours copied (all 26 positions, two layers), finer ones averaged down, coarser ones interpolated from the 8^3 coarse shadow
-// tile (faces: the finite-difference mode for both layers, 4374-4612; edges and corners: TestInterp, 3883-3906), zero-gradient
-// domain faces last (Neumann3D 5929-6004, x-,x+,y-,y+,z-,z+) -- and then applies the operator: the cap of the vorticity on level
+// One workgroup per block builds the TENSORIAL [-2,3) tile of chi exactly as BlockLab::load does for that stencil (phases A-E at
+// W = 2, zero-gradient domain faces: Neumann3D 5929-6004) and then applies the operator: the cap of the vorticity on level
 // levelMaxVorticity - 1, the ordered scan (z, y, x over the block grown by `offset`) for the first cell with 1e-5 < chi < 0.9, which
 // flags the block with 1e10 and ends the scan, and the clearing of interior cells with chi > 0.9 met before it.  The scan is
 // evaluated in parallel through its one order dependence: the position of that first cell (an LDS atomicMin of the scan index).
-__device__ __forceinline__ int lix12(int x, int y, int z) { return ((z + 2) * 12 + (y + 2)) * 12 + (x + 2); }
-
-__global__ void __launch_bounds__(256) k_grad_chi(AmrDev a, const int32_t *__restrict__ finer_row, const int32_t *__restrict__ finer,
-                                                  const int32_t *__restrict__ blevel, int level_max, int lmv, double Rtol, double Ctol,
-                                                  const double *__restrict__ src, double *__restrict__ tmpV) {
-  __shared__ double lab[1728];
-  __shared__ double Ct[512];  // coarse shadow tile, coarse cells [-2,6)^3
+__global__ void __launch_bounds__(256) k_grad_chi(LabDev a, int level_max, int lmv, double Rtol, double Ctol, const double *__restrict__ src, double *__restrict__ tmpV) {
+  constexpr int W = 2, nc = 1;
   __shared__ int first;
-  const int pb = blockIdx.x, t = threadIdx.x;
-  const int32_t *n27 = a.nbr27 + 27 * pb;
-  const int32_t *fin = finer_row[pb] >= 0 ? finer + (size_t)finer_row[pb] * 216 : nullptr;
-  const int par[3] = {a.index[3 * pb] & 1, a.index[3 * pb + 1] & 1, a.index[3 * pb + 2] & 1};
-  bool has_coarse = false;
-  for (int i = 0; i < 27; ++i) has_coarse = has_coarse || n27[i] >= kNbrCoarser;
+#define LABS_SLOT (int)blockIdx.x
+#include "labs_setup.hpp"
+#undef LABS_SLOT
   if (t == 0) first = 0x7fffffff;
-  // A. centre, same-level neighbours, finer neighbours (averaged down)
-  for (int e = t; e < 1728; e += 256) {
-    const int l[3] = {e % 12 - 2, (e / 12) % 12 - 2, e / 144 - 2};
-    int code[3], loc[3], fl[3], q = 0;
-    for (int d = 0; d < 3; ++d) {
-      code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
-      loc[d] = l[d] - 8 * code[d];
-      fl[d] = code[d] < 0 ? 8 + 2 * l[d] : (code[d] > 0 ? 2 * (l[d] - 8) : (2 * l[d]) & 7);
-      if (code[d] == 0 && l[d] >= 4) q |= 1 << d;
-    }
-    const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
-    const int n = n27[icode];
-    double v = 0.0;
-    if (n >= 0 && n < kNbrCoarser) v = src[(size_t)n * 512 + (loc[2] * 8 + loc[1]) * 8 + loc[0]];
-    else if (n == kNbrFiner && fin) v = avg_block(src + (size_t)fin[icode * 8 + q] * 512, fl[0], fl[1], fl[2]);
-    lab[e] = v;
+  {
+    constexpr int c = 0;
+#include "labs_phases.hpp"
   }
-  __syncthreads();
-  if (has_coarse) {
-    // B. coarse shadow tile: own block averaged down, coarser leaves copied, same-level neighbours averaged down
-    for (int e = t; e < 512; e += 256) {
-      const int P[3] = {e % 8 - 2, (e / 8) % 8 - 2, e / 64 - 2};
-      int code[3];
-      for (int d = 0; d < 3; ++d) code[d] = P[d] < 0 ? -1 : (P[d] > 3 ? 1 : 0);
-      const int icode = (code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1);
-      const int n = n27[icode];
-      double v = 0.0;
-      if (icode == 13) {
-        double w[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) w[q] = lab[lix12(2 * P[0] + (q & 1), 2 * P[1] + ((q >> 1) & 1), 2 * P[2] + (q >> 2))];
-        v = avg_down8(w);
-      } else if (n >= kNbrCoarser) {
-        v = src[(size_t)(n - kNbrCoarser) * 512 + ((par[2] * 4 + P[2] + 8) & 7) * 64 + ((par[1] * 4 + P[1] + 8) & 7) * 8 + ((par[0] * 4 + P[0] + 8) & 7)];
-      } else if (n >= 0) {
-        v = avg_block(src + (size_t)n * 512, 2 * P[0] - 8 * code[0], 2 * P[1] - 8 * code[1], 2 * P[2] - 8 * code[2]);
-      }
-      Ct[e] = v;
-    }
-    __syncthreads();
-    // C. zero-gradient domain faces on the coarse tile
-    for (int f = 0; f < 6; ++f) {
-      const int n = a.nbr[pb * 6 + f];
-      if (n >= 0) continue;
-      const int d = f >> 1, side = f & 1, d1 = (d + 1) % 3, d2 = (d + 2) % 3;
-      if (t < 128) {
-        int p[3], q[3];
-        p[d] = side ? 4 + (t >> 6) : -1 - (t >> 6);
-        q[d] = side ? 3 : 0;
-        p[d1] = q[d1] = (t & 7) - 2;
-        p[d2] = q[d2] = ((t >> 3) & 7) - 2;
-        Ct[cix8(p[0], p[1], p[2])] = Ct[cix8(q[0], q[1], q[2])];
-      }
-      __syncthreads();
-    }
-    // D. ghosts behind coarser neighbours
-    for (int e = t; e < 1728; e += 256) {
-      const int l[3] = {e % 12 - 2, (e / 12) % 12 - 2, e / 144 - 2};
-      int code[3], X[3], bit[3], ncode = 0;
-      for (int d = 0; d < 3; ++d) {
-        code[d] = l[d] < 0 ? -1 : (l[d] > 7 ? 1 : 0);
-        ncode += code[d] != 0;
-        X[d] = l[d] >> 1;   // the coarse cell that holds this fine cell (-1 behind the low face, 4 behind the high one)
-        bit[d] = l[d] & 1;  // which of its two children along d
-      }
-      if (ncode == 0 || n27[(code[0] + 1) + 3 * (code[1] + 1) + 9 * (code[2] + 1)] < kNbrCoarser) continue;
-      double v;
-      if (ncode == 1) {  // face: finite-difference mode, both layers
-        const int ax = code[0] ? 0 : (code[1] ? 1 : 2), ax1 = ax == 0 ? 1 : 0, ax2 = ax == 2 ? 1 : 2;
-        const int st1 = ax1 == 0 ? 1 : 8, st2 = ax2 == 1 ? 8 : 64;
-        const int p1 = X[ax1], p2 = X[ax2];
-        const double av = fd_mode_av(Ct + cix8(X[0], X[1], X[2]), p1, p2, st1, st2, bit[ax1], bit[ax2]);
-        int cb[3] = {l[0], l[1], l[2]}, cc[3] = {l[0], l[1], l[2]};
-        cb[ax] = code[ax] > 0 ? 7 : 0;
-        cc[ax] = code[ax] > 0 ? 6 : 1;
-        const double bv = lab[lix12(cb[0], cb[1], cb[2])], cv = lab[lix12(cc[0], cc[1], cc[2])];
-        const int layer = code[ax] < 0 ? -1 - l[ax] : l[ax] - 8;
-        v = fd_mode_blend(av, bv, cv, layer);
-      } else {  // edge / corner: TestInterp
-        v = test_interp([&](int i, int j, int k) -> double { return Ct[cix8(X[0] - 1 + i, X[1] - 1 + j, X[2] - 1 + k)]; }, bit);
-      }
-      lab[e] = v;
-    }
-    __syncthreads();
-  }
-  // E. zero-gradient domain faces on the fine tile: both ghost layers, every transverse position, from the face cell
-  for (int f = 0; f < 6; ++f) {
-    const int n = a.nbr[pb * 6 + f];
-    if (n >= 0) continue;
-    const int d = f >> 1, side = f & 1, d1 = (d + 1) % 3, d2 = (d + 2) % 3;
-    for (int i = t; i < 288; i += 256) {
-      const int layer = i / 144, r = i - 144 * layer;
-      int p[3], q[3];
-      p[d] = side ? 8 + layer : -1 - layer;
-      q[d] = side ? 7 : 0;
-      p[d1] = q[d1] = r % 12 - 2;
-      p[d2] = q[d2] = r / 12 - 2;
-      lab[lix12(p[0], p[1], p[2])] = lab[lix12(q[0], q[1], q[2])];
-    }
-    __syncthreads();
-  }
-  // F. the operator
+  // the operator
   double *T = tmpV + (size_t)pb * 1536;
-  const int level = blevel[pb];
+  const int level = lev;
   if (level == lmv - 1 && lmv < level_max) {  // 8546-8557
     for (int c = t; c < 512; c += 256) {
       const double u0 = T[c], u1 = T[512 + c], u2 = T[1024 + c];
@@ -582,7 +430,7 @@ __global__ void __launch_bounds__(256) k_grad_chi(AmrDev a, const int32_t *__res
   __syncthreads();
   const int stop = first;
   for (int c = t; c < 512; c += 256) {
-    const int x = c & 7, y = (c >> 3) & 7, z = c >> 6, e = lix12(x, y, z);
+    const int x = c & 7, y = (c >> 3) & 7, z = c >> 6, e = lix(x, y, z);
     double v = lab[e];
     v = v < 1.0 ? v : 1.0;
     if (v > 0.9 && e < stop) { T[c] = 0.0; T[512 + c] = 0.0; T[1024 + c] = 0.0; }  // 8592-8597
@@ -593,6 +441,35 @@ __global__ void __launch_bounds__(256) k_grad_chi(AmrDev a, const int32_t *__res
     T[(cz[t] * 8 + cy[t]) * 8 + cx[t]] = 1e10;
   }
 }
+#undef LABS_BLOCK
+#undef LABS_CELL
+
+// the same as k_labs for the local blocks of a rank's tensorial view: tables of the view, ghost blocks in the pool
+#define LABS_BLOCK(slot, c) src.blk(slot, nc, c)
+#define LABS_CELL(slot, c, i) src.blk(slot, nc, c)[i]
+#define LABS_SLOT slots ? slots[blockIdx.x] : first + (int)blockIdx.x
+#define LABS_AFTER_SLOT double *__restrict__ tile = out + (size_t)blockIdx.x * L3 * nc;
+template <int W>
+__global__ void __launch_bounds__(256) k_labs_view(LabDev a, const int32_t *__restrict__ slots, int first, int star, LabSrcView src, int nc, double *__restrict__ out) {
+#include "labs_setup.hpp"
+  for (int c = 0; c < nc; ++c) {
+#include "labs_phases.hpp"
+    // F, as in k_labs
+    for (int e = t; e < L3; e += 256) {
+      double v = lab[e];
+      if (W <= 2 && star) {
+        const int x = e % L - W, y = (e / L) % L - W, z = e / (L * L) - W;
+        if ((x < 0 || x > 7) + (y < 0 || y > 7) + (z < 0 || z > 7) > 1) v = __builtin_nan("");
+      }
+      tile[(size_t)e * nc + c] = v;
+    }
+    __syncthreads();
+  }
+}
+#undef LABS_SLOT
+#undef LABS_AFTER_SLOT
+#undef LABS_BLOCK
+#undef LABS_CELL
 
 // unchanged blocks: copy; parents of compressed octets: compress (5272-5329) -- pairs[n][2] = dst slot, src slot;
 // octets[n][9] = dst slot, eight src slots (child = I + 2J + 4K)
@@ -689,6 +566,70 @@ __global__ void __launch_bounds__(256) k_unpack_blocks(const double *__restrict_
 }
 }  // namespace
 
+// The finer leaves behind every kNbrFiner position of the blocks [0, nloc) of `mo`, by octant of the block (bits of x, y, z >= 4):
+// finer_row[b] = the block's row of finer[rows][27][8] (-1: no finer neighbour), -1 in the row where nothing is read.  Throws what
+// Grid::leaf throws.
+static void finer_tables(const Grid *mo, int64_t nloc, std::vector<int32_t> &finer_row, std::vector<int32_t> &finer) {
+  finer_row.assign((size_t)nloc, -1);
+  for (int64_t b = 0; b < nloc; ++b) {
+    bool any = false;
+    for (int c = 0; c < 27; ++c) any = any || mo->nbr27[27 * (size_t)b + c] == kNbrFiner;
+    if (!any) continue;
+    finer_row[b] = (int32_t)(finer.size() / 216);
+    finer.resize(finer.size() + 216, -1);
+    int32_t *row = finer.data() + finer.size() - 216;
+    const int l = mo->blevel[b];
+    for (int icode = 0; icode < 27; ++icode) {
+      if (mo->nbr27[27 * (size_t)b + icode] != kNbrFiner) continue;
+      const int code[3] = {icode % 3 - 1, (icode / 3) % 3 - 1, icode / 9 - 1};
+      for (int q = 0; q < 8; ++q) {
+        int fi[3];
+        bool used = true;
+        for (int d = 0; d < 3; ++d) {
+          const int bit = (q >> d) & 1;
+          if (code[d] != 0 && bit) used = false;
+          fi[d] = 2 * mo->index[3 * (size_t)b + d] + (code[d] < 0 ? -1 : (code[d] > 0 ? 2 : bit));
+        }
+        if (used) row[icode * 8 + q] = mo->leaf(l + 1, fi);
+      }
+    }
+  }
+  if (finer.empty()) finer.assign(216, -1);
+}
+
+// The five index tables of a LabDev on the device, for the blocks [0, nloc) of `mo` (a multi-level mesh object: the mesh itself on one
+// rank, a rank's tensorial view over ranks).  One owner for the four users: cup3d_sim_labs and cup3d_sim_labs_over_ranks keep theirs in
+// the sim, mesh adaptation and GradChiOnTmp build one per call and let it go after their stream synchronise.
+struct LabIndex {
+  int32_t *n27 = nullptr, *index = nullptr, *level = nullptr, *finer_row = nullptr, *finer = nullptr;
+  std::vector<int32_t> h_finer_row, h_finer;  // the two tables `mo` does not hold, on the host
+  size_t bytes = 0;                           // of the five tables
+  LabIndex() = default;
+  LabIndex(const LabIndex &) = delete;
+  int build(const Grid *mo, int64_t nloc, const char *who) {
+    try {
+      finer_tables(mo, nloc, h_finer_row, h_finer);
+    } catch (const std::exception &e) {
+      set_error("%s: %s", who, e.what());
+      return CUP3D_EINVAL;
+    }
+    const std::pair<int32_t **, const std::vector<int32_t> *> tables[] = {{&n27, &mo->nbr27}, {&index, &mo->index}, {&level, &mo->blevel}, {&finer_row, &h_finer_row}, {&finer, &h_finer}};
+    for (const auto &[d, v] : tables) {
+      CUP3D_HIP(hipMalloc((void **)d, std::max<size_t>(v->size(), 1) * sizeof(int32_t)));
+      if (!v->empty()) CUP3D_HIP(hipMemcpy(*d, v->data(), v->size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      bytes += v->size() * sizeof(int32_t);
+    }
+    return CUP3D_OK;
+  }
+  // box and boundary conditions come from `g`: the sim's grid, or the mesh object itself
+  LabDev dev(const Grid *g, int bc_comp) const {
+    return LabDev{n27, index, level, finer_row, finer, {g->bpd[0], g->bpd[1], g->bpd[2]}, {g->bc[0], g->bc[1], g->bc[2]}, bc_comp};
+  }
+  ~LabIndex() {
+    for (void *p : {(void *)n27, (void *)index, (void *)level, (void *)finer_row, (void *)finer})
+      if (p) (void)hipFree(p);
+  }
+};
 
 // ---- data movement of MeshAdaptation::Adapt, shared by the one-rank and the multi-rank entry points.
 // `mo`: the OLD mesh as this rank sees it (a whole mesh, or a tensorial rank view whose ghost slots of `fs` hold the owners' data);
@@ -696,7 +637,7 @@ __global__ void __launch_bounds__(256) k_unpack_blocks(const double *__restrict_
 // one (refine_1 + RefineBlocks, 5227-5249, 5493-5565) or the parent of an octet of them (compress, 5272-5329).
 struct NewBlock { int level, idx[3]; int32_t dst; };
 static int adapt_produce(const Grid *mo, const std::vector<NewBlock> &blocks, const double *fs, double *fd, int nc) {
-  std::vector<int32_t> pairs, octets, items, finer;
+  std::vector<int32_t> pairs, octets, items;
   try {
     std::vector<int32_t> item_of((size_t)mo->Z.size(), -1);
     for (const NewBlock &nbk : blocks) {
@@ -728,46 +669,38 @@ static int adapt_produce(const Grid *mo, const std::vector<NewBlock> &blocks, co
     // list holds -- impossible, since all eight go where the parent is refined
     for (size_t i = 0; i < items.size(); ++i)
       if (items[i] < 0) throw std::invalid_argument("a refined block lacks some of its children in the new mesh");
-    // finer leaves behind every code of the refined parents, by octant of the parent
-    finer.assign(items.size() / 9 * 27 * 8, -1);
-    for (size_t it = 0; it < items.size() / 9; ++it) {
-      const int32_t pb = items[9 * it];
-      const int l = mo->blevel[pb];
-      for (int icode = 0; icode < 27; ++icode) {
-        if (mo->nbr27[27 * (size_t)pb + icode] != kNbrFiner) continue;
-        const int code[3] = {icode % 3 - 1, (icode / 3) % 3 - 1, icode / 9 - 1};
-        for (int q = 0; q < 8; ++q) {
-          int fi[3];
-          bool used = true;
-          for (int d = 0; d < 3; ++d) {
-            const int bit = (q >> d) & 1;
-            if (code[d] != 0 && bit) used = false;
-            fi[d] = 2 * mo->index[3 * (size_t)pb + d] + (code[d] < 0 ? -1 : (code[d] > 0 ? 2 : bit));
-          }
-          if (!used) continue;
-          const int32_t fl = mo->leaf(l + 1, fi);
-          if (fl < 0) throw std::invalid_argument("a finer neighbour of a refined block is not visible on this rank");
-          finer[(it * 27 + icode) * 8 + q] = fl;
-        }
-      }
-    }
   } catch (const std::exception &e) {
     set_error("mesh adaptation: %s", e.what());
     return CUP3D_EINVAL;
   }
-  DevInts d_pairs, d_octets, d_items, d_finer, d_n27, d_nbr, d_index;
+  LabIndex tab;
+  DevInts d_pairs, d_octets, d_items;
   int rc;
-  if ((rc = d_pairs.upload(pairs)) || (rc = d_octets.upload(octets)) || (rc = d_items.upload(items)) || (rc = d_finer.upload(finer))) return rc;
+  if (!items.empty()) {
+    if ((rc = tab.build(mo, mo->nblocks(), "mesh adaptation"))) return rc;
+    // phase A of k_refine averages down every finer leaf behind a refined parent: entry [code][octant] of the parent's row is read
+    // unless the octant is an upper one along an axis the code leaves the block by
+    for (size_t it = 0; it < items.size(); it += 9) {
+      const int32_t pb = items[it], r = tab.h_finer_row[pb];
+      for (int i = 0; r >= 0 && i < 216; ++i) {
+        const int icode = i >> 3, q = i & 7;
+        const bool read = !((q & 1) && icode % 3 != 1) && !((q & 2) && (icode / 3) % 3 != 1) && !((q & 4) && icode / 9 != 1);
+        if (read && mo->nbr27[27 * (size_t)pb + icode] == kNbrFiner && tab.h_finer[216 * (size_t)r + i] < 0) {
+          set_error("mesh adaptation: a finer neighbour of a refined block is not visible on this rank");
+          return CUP3D_EINVAL;
+        }
+      }
+    }
+  }
+  if ((rc = d_pairs.upload(pairs)) || (rc = d_octets.upload(octets)) || (rc = d_items.upload(items))) return rc;
   ProfileScope ps("adapt_transfer");
   if (!pairs.empty()) hipLaunchKernelGGL(k_copy_blocks, dim3((unsigned)(pairs.size() / 2)), dim3(256), 0, stream(), d_pairs.p, fs, fd, nc);
   if (!octets.empty()) hipLaunchKernelGGL(k_compress_blocks, dim3((unsigned)(octets.size() / 9)), dim3(256), 0, stream(), d_octets.p, fs, fd, nc);
   if (!items.empty()) {
-    if ((rc = d_n27.upload(mo->nbr27)) || (rc = d_nbr.upload(mo->nbr)) || (rc = d_index.upload(mo->index))) return rc;
-    AmrDev a{nullptr, nullptr, d_n27.p, d_nbr.p, d_index.p, -1};
-    RefineTab tab{d_items.p, d_finer.p};
+    const LabDev a = tab.dev(mo, -1);
     const unsigned n = (unsigned)(items.size() / 9);
-    if (nc == 3) hipLaunchKernelGGL(k_refine<3>, dim3(n), dim3(256), 0, stream(), a, tab, fs, fd);
-    else hipLaunchKernelGGL(k_refine<1>, dim3(n), dim3(256), 0, stream(), a, tab, fs, fd);
+    if (nc == 3) hipLaunchKernelGGL(k_refine<3>, dim3(n), dim3(256), 0, stream(), a, (const int32_t *)d_items.p, fs, fd);
+    else hipLaunchKernelGGL(k_refine<1>, dim3(n), dim3(256), 0, stream(), a, (const int32_t *)d_items.p, fs, fd);
   }
   CUP3D_HIP(hipGetLastError());
   CUP3D_HIP(hipStreamSynchronize(stream()));  // the index tables above are freed on return
@@ -895,55 +828,13 @@ extern "C" int cup3d_adapt_migrate(const cup3d_grid_t *old_mesh_h, const int32_t
 // the resident chi; with cup3d_compute_vorticity before and cup3d_tag_blocks after it, adaptMesh's decision input is complete for
 // runs with obstacles.  `mo`: a multi-level mesh object whose first `nloc` slots are the blocks of `tmpV` (the mesh itself on one
 // rank, the rank's TENSORIAL view over ranks -- the tensorial chi tile reaches edge / corner neighbours); `chi` lives on mo's slots.
-// The finer leaves behind every kNbrFiner position of the blocks [0, nloc) of `mo`, by octant of the block (bits of x, y, z >= 4):
-// finer_row[b] = the block's row of finer[rows][27][8] (-1: no finer neighbour), -1 in the row where nothing is read.  Throws what
-// Grid::leaf throws.
-static void finer_tables(const Grid *mo, int64_t nloc, std::vector<int32_t> &finer_row, std::vector<int32_t> &finer) {
-  finer_row.assign((size_t)nloc, -1);
-  for (int64_t b = 0; b < nloc; ++b) {
-    bool any = false;
-    for (int c = 0; c < 27; ++c) any = any || mo->nbr27[27 * (size_t)b + c] == kNbrFiner;
-    if (!any) continue;
-    finer_row[b] = (int32_t)(finer.size() / 216);
-    finer.resize(finer.size() + 216, -1);
-    int32_t *row = finer.data() + finer.size() - 216;
-    const int l = mo->blevel[b];
-    for (int icode = 0; icode < 27; ++icode) {
-      if (mo->nbr27[27 * (size_t)b + icode] != kNbrFiner) continue;
-      const int code[3] = {icode % 3 - 1, (icode / 3) % 3 - 1, icode / 9 - 1};
-      for (int q = 0; q < 8; ++q) {
-        int fi[3];
-        bool used = true;
-        for (int d = 0; d < 3; ++d) {
-          const int bit = (q >> d) & 1;
-          if (code[d] != 0 && bit) used = false;
-          fi[d] = 2 * mo->index[3 * (size_t)b + d] + (code[d] < 0 ? -1 : (code[d] > 0 ? 2 : bit));
-        }
-        if (used) row[icode * 8 + q] = mo->leaf(l + 1, fi);
-      }
-    }
-  }
-  if (finer.empty()) finer.assign(216, -1);
-}
-
 static int grad_chi_run(const Grid *mo, int64_t nloc, const double *chi, double *tmpV, double Rtol, double Ctol, int level_max_vorticity) {
-  std::vector<int32_t> finer_row, finer;
-  try {
-    finer_tables(mo, nloc, finer_row, finer);
-  } catch (const std::exception &e) {
-    set_error("cup3d_grad_chi_on_tmp: %s", e.what());
-    return CUP3D_EINVAL;
-  }
-  DevInts d_row, d_finer, d_n27, d_nbr, d_index, d_level;
-  int rc;
-  if ((rc = d_row.upload(finer_row)) || (rc = d_finer.upload(finer)) || (rc = d_n27.upload(mo->nbr27)) || (rc = d_nbr.upload(mo->nbr)) ||
-      (rc = d_index.upload(mo->index)) || (rc = d_level.upload(mo->blevel)))
-    return rc;
-  AmrDev a{nullptr, nullptr, d_n27.p, d_nbr.p, d_index.p, -1};
+  LabIndex tab;
+  int rc = tab.build(mo, nloc, "cup3d_grad_chi_on_tmp");
+  if (rc) return rc;
   {
     ProfileScope ps("grad_chi_on_tmp");
-    hipLaunchKernelGGL(k_grad_chi, dim3((unsigned)nloc), dim3(256), 0, stream(), a, d_row.p, d_finer.p, d_level.p, mo->level_max, level_max_vorticity, Rtol, Ctol, chi,
-                       tmpV);
+    hipLaunchKernelGGL(k_grad_chi, dim3((unsigned)nloc), dim3(256), 0, stream(), tab.dev(mo, -1), mo->level_max, level_max_vorticity, Rtol, Ctol, chi, tmpV);
   }
   CUP3D_HIP(hipGetLastError());
   CUP3D_HIP(hipStreamSynchronize(stream()));  // the tables above are freed on return
@@ -1021,91 +912,15 @@ extern "C" int cup3d_debug_amr_slabs(cup3d_sim_t *h, int field, int w, double *o
 }
 #endif
 
-// ==== cup3d_sim_labs / cup3d_sim_labs_device.  Ghosted block tiles of any stencil box on demand: BlockLab::load + post_load (main.cpp:3623-3787) for a list of blocks.
-// It lives in this file because it uses the device helpers above -- avg_down8 / avg_block, fd_mode_av / fd_mode_blend (with interp1d),
-// test_interp -- and the finer-leaf tables of k_grad_chi, none of them restated.
-//
-// The stencil kernels build the three tile shapes they need in LDS and never hand them out; this is the general operation for a
-// consumer OUTSIDE the library (the kernel-functor protocol of compute<Lab>): block b with its ghosts for the box [-w, w+1)^3,
-// w = 1..4, star or tensorial, in the reference's Matrix3D layout [L][L][L][nc] (x fastest, component innermost, L = 8 + 2w).
-// One workgroup per tile, one component at a time in LDS (16^3 fine cells + the 10^3 coarse shadow tile = 40 768 B), in the
-// reference's order:
-//   A. interior copy, SameLevelExchange (3823-3876), FineToCoarseExchange = AverageDown of the finer leaves (3907-4065);
-//   B. the coarse shadow tile m_CoarsenedBlock: coarser leaves copied (CoarseFineExchange 4066-4170), same-level neighbours
-//      averaged down (FillCoarseVersion 4171-4235; every one of them -- the cells the UseCoarseStencil rule 3788-3822 would leave
-//      out are read by no interpolation: tests/test_gpu_labs.py::test_tiles_equal_the_reference, the reference's own tiles on four
-//      meshes, is the test that a violation would turn red), the block's own average-down (post_load 3750-3778);
-//   C. _apply_bc on the coarse tile (3781): ordered passes x, y, z, each over the whole ghost slab;
-//   D. CoarseFineInterpolation (4236-4614): TestInterp everywhere behind a coarser neighbour, then the finite-difference mode with
-//      the 1/15 blend on the two layers next to a FACE (it overwrites TestInterp there, as in the reference);
-//   E. _apply_bc on the fine tile: ordered passes x, y, z, each over the whole ghost slab, transverse ghosts of earlier passes included;
-//   F. the cells the reference leaves undefined -- edge and corner ghosts of a star tile with w <= 2, where use_averages (3618-3621)
-//      does not hold -- leave as quiet NaN, so that a consumer that reads them sees it.
-// A tile with w >= 3 is built tensorially by the reference whatever the stencil says (use_averages), so `tensorial` only decides F.
-// The kernel reads blocks only: it neither needs nor touches the ghost slabs the stencil kernels keep behind kNbrHalo.
+// ==== cup3d_sim_labs / cup3d_sim_labs_device: the host side of k_labs (the kernels and what they do: "ghosted block tiles" above)
 namespace cup3d {
-
-struct LabDev {
-  const int32_t *n27;        // [nb][27]
-  const int32_t *index;      // [nb][3]
-  const int32_t *level;      // [nb]
-  const int32_t *finer_row;  // [nb]: row of `finer`, or -1
-  const int32_t *finer;      // [rows][27][8]
-  int bpd[3], bc[3];
-  int bc_comp;  // scalar fields: -1 = zero-gradient domain faces (ScalarLab); k = element of BlockLabBC<.., direction k>
-};
-
-constexpr int kLabCoarse = 10;  // coarse shadow tile: coarse cells [-3, 7)^3 (w = 4 reads [-3, 6])
-__device__ __forceinline__ int cix10(int X, int Y, int Z) { return ((Z + 3) * kLabCoarse + (Y + 3)) * kLabCoarse + (X + 3); }
-
-// domain-face rule of one tile value: the vector lab negates every component at a wall and the normal one at a freespace face
-// (6107-6503), the scalar lab copies (6561-6581), the scalar of BlockLabBC<.., direction k> behaves as component k of a vector
-__device__ __forceinline__ double lab_bc_value(double v, int nc, int c, int bc_comp, int bc_kind, int d) {
-  const int cc = nc == 3 ? c : bc_comp;
-  return (cc >= 0 && (bc_kind == CUP3D_BC_WALL || cc == d)) ? -v : v;
-}
-
-// Phases A-F live once, in labs_body.hpp, and are included into the two kernels below, which differ in where the blocks of a tile's
-// neighbourhood live.  k_labs, one rank: every slot is a row of the field array.  k_labs_view, a mesh spread over ranks
-// (cup3d_sim_labs_over_ranks): slots [0, n_local) of the rank's tensorial view are rows of the sim's own field array, read in place; a
-// ghost slot is a row of the call's ghost pool, found through pool_of (-1: not fetched -- row 0 of the pool, which holds NaN, so that
-// a read the request plan did not foresee shows in the tile instead of leaving the buffer).
-struct LabSrcView {
-  const double *__restrict__ field;
-  const double *__restrict__ pool;      // [1 + fetched ghosts][nc][512]
-  const int32_t *__restrict__ pool_of;  // [nghost]
-  int n_local;
-  __device__ __forceinline__ const double *blk(int slot, int nc, int c) const {
-    if (slot < n_local) return field + ((size_t)slot * nc + c) * 512;
-    return pool + ((size_t)(pool_of[slot - n_local] + 1) * nc + c) * 512;
-  }
-};
-
-template <int W>
-__global__ void __launch_bounds__(256) k_labs(LabDev a, const int32_t *__restrict__ slots, int first, int star, const double *__restrict__ src, int nc,
-                                              double *__restrict__ out) {
-#define LABS_BLOCK(slot, c) (src + ((size_t)(slot) * nc + (c)) * 512)
-#define LABS_CELL(slot, c, i) src[((size_t)(slot) * nc + (c)) * 512 + (i)]
-#include "labs_body.hpp"
-#undef LABS_BLOCK
-#undef LABS_CELL
-}
-// the same for the local blocks of a rank's tensorial view: tables of the view, ghost blocks in the pool
-template <int W>
-__global__ void __launch_bounds__(256) k_labs_view(LabDev a, const int32_t *__restrict__ slots, int first, int star, LabSrcView src, int nc, double *__restrict__ out) {
-#define LABS_BLOCK(slot, c) src.blk(slot, nc, c)
-#define LABS_CELL(slot, c, i) src.blk(slot, nc, c)[i]
-#include "labs_body.hpp"
-#undef LABS_BLOCK
-#undef LABS_CELL
-}
 
 // ---- host side
 constexpr size_t kLabStageBytes = (size_t)64 << 20;  // device staging buffer of the host variant
 constexpr long kLabSlotCap = 8192;                   // listed tiles per launch (the smallest tile, 10^3 doubles, fills the buffer with as many)
 
 struct LabTables {
-  int32_t *n27 = nullptr, *index = nullptr, *level = nullptr, *finer_row = nullptr, *finer = nullptr;
+  LabIndex tab;
   int32_t *d_slots = nullptr, *h_slots = nullptr;  // slot list of one launch: device copy, pinned host copy
   hipEvent_t ev_slots = nullptr;                   // the upload that last read h_slots
   bool slots_in_flight = false;
@@ -1117,8 +932,8 @@ void labs_destroy(Sim *s) {
   labs_view_destroy(s);  // the cached view, its tables and the ghost pool of cup3d_sim_labs_over_ranks
   LabTables *T = s->labs;
   if (!T) return;
-  void *dev[] = {T->n27, T->index, T->level, T->finer_row, T->finer, T->d_slots, T->stage};
-  for (void *p : dev) if (p) (void)hipFree(p);
+  if (T->d_slots) (void)hipFree(T->d_slots);
+  if (T->stage) (void)hipFree(T->stage);
   if (T->h_slots) (void)hipHostFree(T->h_slots);
   if (T->ev_slots) (void)hipEventDestroy(T->ev_slots);
   delete T;
@@ -1130,28 +945,20 @@ static int labs_prepare(Sim *s, bool want_stage) {
   if (!s->labs) {
     std::unique_ptr<Grid> tmp;
     const Grid *mo = s->grid;
-    std::vector<int32_t> finer_row, finer;
     try {
       if (!mo->multilevel) { tmp = mo->as_mesh(); mo = tmp.get(); }
-      finer_tables(mo, mo->nblocks(), finer_row, finer);
     } catch (const std::exception &e) {
       set_error("cup3d_sim_labs: %s", e.what());
       return CUP3D_EINVAL;
     }
     s->labs = new LabTables();
     LabTables *T = s->labs;
-    auto up = [&](int32_t **d, const std::vector<int32_t> &v) -> int {
-      CUP3D_HIP(hipMalloc((void **)d, std::max<size_t>(v.size(), 1) * sizeof(int32_t)));
-      if (!v.empty()) CUP3D_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      s->bytes += v.size() * sizeof(int32_t);
-      return CUP3D_OK;
-    };
-    int rc;
-    if ((rc = up(&T->n27, mo->nbr27)) || (rc = up(&T->index, mo->index)) || (rc = up(&T->level, mo->blevel)) || (rc = up(&T->finer_row, finer_row)) ||
-        (rc = up(&T->finer, finer))) {
+    int rc = T->tab.build(mo, mo->nblocks(), "cup3d_sim_labs");
+    if (rc) {
       labs_destroy(s);
       return rc;
     }
+    s->bytes += T->tab.bytes;
     hipError_t e = hipMalloc((void **)&T->d_slots, kLabSlotCap * sizeof(int32_t));
     if (e == hipSuccess) e = hipHostMalloc((void **)&T->h_slots, kLabSlotCap * sizeof(int32_t), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&T->ev_slots, hipEventDisableTiming);
@@ -1171,8 +978,7 @@ static int labs_prepare(Sim *s, bool want_stage) {
 // tiles [t0, t0 + m) of the request -> out (device), on the compute stream; m <= kLabSlotCap when slots are listed
 static int labs_launch(Sim *s, const double *f, int nc, long t0, long m, const int32_t *slots, int w, int tensorial, int bc_comp, double *out) {
   LabTables *T = s->labs;
-  const Grid *g = s->grid;
-  LabDev a{T->n27, T->index, T->level, T->finer_row, T->finer, {g->bpd[0], g->bpd[1], g->bpd[2]}, {g->bc[0], g->bc[1], g->bc[2]}, nc == 1 ? bc_comp : -1};
+  const LabDev a = T->tab.dev(s->grid, nc == 1 ? bc_comp : -1);
   const int32_t *d_slots = nullptr;
   if (slots) {
     if (T->slots_in_flight) CUP3D_HIP(hipEventSynchronize(T->ev_slots));  // the pinned copy is free again
@@ -1280,8 +1086,7 @@ struct LabsView {
   std::vector<int32_t> key_level, key_owner;
   std::vector<int64_t> key_Z;
   std::unique_ptr<Grid> tv;
-  int32_t *n27 = nullptr, *index = nullptr, *level = nullptr, *finer_row = nullptr, *finer = nullptr;  // tables of k_labs_view (local rows of tv)
-  size_t table_bytes = 0;
+  LabIndex tab;  // tables of k_labs_view (local rows of tv)
   // one call's plan, host side (members: the uploads read them after the functions that fill them returned) ...
   std::vector<uint8_t> gbox, sbox, rbox;
   std::vector<double> h_req, h_got;
@@ -1295,11 +1100,9 @@ struct LabsView {
 static void labs_view_destroy(Sim *s) {
   LabsView *V = s->labs_view;
   if (!V) return;
-  void *dev[] = {V->n27, V->index, V->level, V->finer_row, V->finer};
-  for (void *p : dev) if (p) (void)hipFree(p);
   DevGrow *g[] = {&V->d_req, &V->d_got, &V->d_pool_of, &V->d_sslots, &V->d_sbox, &V->d_soff, &V->d_rbox, &V->d_roff, &V->d_pack, &V->d_recv, &V->d_pool, &V->d_slots, &V->d_stage};
   for (DevGrow *b : g) b->release(s);
-  s->bytes -= V->table_bytes;
+  s->bytes -= V->tab.bytes;
   delete V;
   s->labs_view = nullptr;
 }
@@ -1315,7 +1118,6 @@ static int labs_view_get(Sim *s, const Grid *gm, const int32_t *owner, LabsView 
   }
   labs_view_destroy(s);
   std::unique_ptr<Grid> tv;
-  std::vector<int32_t> finer_row, finer;
   try {
     for (int d = 0; d < 3; ++d)
       if (gm->bpd[d] != g->bpd[d] || gm->bc[d] != g->bc[d]) throw std::invalid_argument("mesh and sim belong to different boxes");
@@ -1325,23 +1127,15 @@ static int labs_view_get(Sim *s, const Grid *gm, const int32_t *owner, LabsView 
     if (tv->n_local != s->nb) throw std::invalid_argument("the sim does not hold this rank's blocks of the mesh");
     for (int64_t b = 0; b < s->nb; ++b)
       if (tv->blevel[b] != (g->multilevel ? g->blevel[b] : g->level) || tv->Z[b] != g->Z[b]) throw std::invalid_argument("the sim's blocks are not this rank's leaves of the mesh (level, Z)");
-    finer_tables(tv.get(), tv->n_local, finer_row, finer);
   } catch (const std::exception &e) {
     set_error("cup3d_sim_labs_over_ranks: %s", e.what());
     return CUP3D_EINVAL;
   }
   V = new LabsView();
   s->labs_view = V;
-  auto up = [&](int32_t **d, const std::vector<int32_t> &v) -> int {
-    CUP3D_HIP(hipMalloc((void **)d, std::max<size_t>(v.size(), 1) * sizeof(int32_t)));
-    if (!v.empty()) CUP3D_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    V->table_bytes += v.size() * sizeof(int32_t);
-    s->bytes += v.size() * sizeof(int32_t);
-    return CUP3D_OK;
-  };
-  int rc;
-  if ((rc = up(&V->n27, tv->nbr27)) || (rc = up(&V->index, tv->index)) || (rc = up(&V->level, tv->blevel)) || (rc = up(&V->finer_row, finer_row)) ||
-      (rc = up(&V->finer, finer))) {
+  const int rc = V->tab.build(tv.get(), tv->n_local, "cup3d_sim_labs_over_ranks");
+  s->bytes += V->tab.bytes;  // labs_view_destroy takes them off again
+  if (rc) {
     labs_view_destroy(s);
     return rc;
   }
@@ -1482,8 +1276,7 @@ static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int
     CUP3D_HIP(hipStreamSynchronize(stream()));
     return CUP3D_OK;
   }
-  const Grid *g = s->grid;
-  LabDev a{V->n27, V->index, V->level, V->finer_row, V->finer, {g->bpd[0], g->bpd[1], g->bpd[2]}, {g->bc[0], g->bc[1], g->bc[2]}, nc == 1 ? scalar_dir : -1};
+  const LabDev a = V->tab.dev(s->grid, nc == 1 ? scalar_dir : -1);
   LabSrcView src{f, (const double *)V->d_pool.p, (const int32_t *)V->d_pool_of.p, (int)tv->n_local};
   const int star = tensorial ? 0 : 1;
   const size_t L = 8 + 2 * (size_t)width, tile = L * L * L * nc;

@@ -330,7 +330,7 @@ static void star_boxes(const Grid &G, const int32_t *owner, int r, int W, std::m
   }
 }
 
-// The tile consumers' counterpart of star_boxes, on a tensorial rank view (grid.hpp): phases A and B of the tile kernels (labs_body.hpp) are the only
+// The tile consumers' counterpart of star_boxes, on a tensorial rank view (grid.hpp): phases A and B of the tile kernels (labs_phases.hpp) are the only
 // ones that read blocks -- C to F work on the two tiles in LDS -- and they are replayed here cell by cell with the kernel's own
 // expressions, so that a change there has one place to be repeated in.  Blocks whose 27 positions are all local are skipped.
 void Grid::lab_boxes(const int32_t *slots, int64_t n, int W, std::vector<uint8_t> &box) const {

@@ -1,35 +1,10 @@
-// Phases A-F of the ghosted-tile kernels (amr.hip, "cup3d_sim_labs"): the BODY of k_labs<W> and of k_labs_view<W>, included into each
-// of the two between the kernel's braces, so that it exists once.  (A __device__ function template on the block source was the first
-// form; inlined, it compiled k_labs to other register figures than the ones tests/test_labs_kernel_resources.py holds it to -- 5 and 4
-// scalar registers parked in VGPR lanes at w = 2 and 3 instead of 2 -- whichever way the source was passed.  Included as text, k_labs is
-// token for token the kernel it was.)  The includer provides
-//   a, slots, first, star, nc, out    the kernel's parameters of those names (LabDev, slot list or first slot, star flag, components, tiles)
+// Phases A-E of BlockLab::load + post_load for ONE component c of the block pb, behind labs_setup.hpp: they end with the fine tile of
+// that component complete in lab[] behind a barrier, the caller's to consume (and to put a barrier behind, before lab[] is reused).
+// The includer provides, besides what the set-up took and made,
+//   nc, c                             number of components of the field, the component
 //   LABS_BLOCK(slot, c)               pointer to component c of block `slot` (512 doubles)
 //   LABS_CELL(slot, c, i)             cell i of it
 // Grid::lab_boxes (grid.cpp) replays the block reads of phases A and B on the host: a change to them is repeated there.
-  constexpr int L = 8 + 2 * W, L3 = L * L * L, C3 = kLabCoarse * kLabCoarse * kLabCoarse;
-  __shared__ double lab[L3];
-  __shared__ double Ct[C3];
-  const int t = threadIdx.x;
-  const int pb = slots ? slots[blockIdx.x] : first + (int)blockIdx.x;
-  double *__restrict__ tile = out + (size_t)blockIdx.x * L3 * nc;
-  const int32_t *n27 = a.n27 + 27 * (size_t)pb;
-  const int32_t *fin = a.finer_row[pb] >= 0 ? a.finer + (size_t)a.finer_row[pb] * 216 : nullptr;
-  const int idx[3] = {a.index[3 * pb], a.index[3 * pb + 1], a.index[3 * pb + 2]};
-  const int par[3] = {idx[0] & 1, idx[1] & 1, idx[2] & 1};
-  const int lev = a.level[pb];
-  bool has_coarse = false;
-  for (int i = 0; i < 27; ++i) has_coarse = has_coarse || n27[i] >= kNbrCoarser;
-  // domain faces of this block: bit f of `dom` (f = x-, x+, y-, y+, z-, z+) where a boundary condition sits behind the face
-  int dom = 0;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    if (a.bc[d] == CUP3D_BC_PERIODIC) continue;
-    if (idx[d] == 0) dom |= 1 << (2 * d);
-    if (idx[d] == (a.bpd[d] << lev) - 1) dom |= 2 << (2 * d);
-  }
-  auto lix = [](int x, int y, int z) { return ((z + W) * L + (y + W)) * L + (x + W); };
-  for (int c = 0; c < nc; ++c) {
     const double *__restrict__ own = LABS_BLOCK(pb, c);
     // A. centre, same-level neighbours, finer neighbours (averaged down)
     for (int e = t; e < L3; e += 256) {
@@ -140,14 +115,3 @@
       }
       __syncthreads();
     }
-    // F. the tile leaves in the reference's layout; what the reference leaves undefined leaves as NaN
-    for (int e = t; e < L3; e += 256) {
-      double v = lab[e];
-      if (W <= 2 && star) {
-        const int x = e % L - W, y = (e / L) % L - W, z = e / (L * L) - W;
-        if ((x < 0 || x > 7) + (y < 0 || y > 7) + (z < 0 || z > 7) > 1) v = __builtin_nan("");
-      }
-      tile[(size_t)e * nc + c] = v;
-    }
-    __syncthreads();
-  }

@@ -60,6 +60,12 @@ class Obstacle(C.Structure):
                 ("force", C.c_double * 3), ("torque", C.c_double * 3)]
 
 
+class ObstacleMotion(C.Structure):
+    """cup3d_obstacle_motion"""
+    _fields_ = [("forced", C.c_int * 3), ("block_rotation", C.c_int * 3), ("vel_imposed", C.c_double * 3), ("block_sums", C.c_void_p),
+                ("totals", C.c_double * 29), ("vel_computed", C.c_double * 3), ("omega_computed", C.c_double * 3)]
+
+
 class ObstacleSurface(C.Structure):
     """cup3d_obstacle_surface"""
     _fields_ = [("nblocks", C.c_long), ("slots", C.c_void_p), ("first", C.c_void_p), ("ijk", C.c_void_p), ("dchi", C.c_void_p), ("udef", C.c_void_p),
@@ -152,6 +158,7 @@ SIGNATURES = {
     "cup3d_diffusion_solve": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.POINTER(PoissonParams), C.POINTER(PoissonResult)]),
     "cup3d_penalization": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Obstacle)]),
     "cup3d_update_tmpv": (C.c_int, [_vp, C.c_int, C.POINTER(Obstacle)]),
+    "cup3d_update_obstacles": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Obstacle), C.POINTER(ObstacleMotion)]),
     "cup3d_compute_forces": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_compute_forces_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_profile_enable": (C.c_int, [C.c_int]),

@@ -485,12 +485,17 @@ class ObstacleData:
     """Host-side description of one obstacle for the device operators: the non-null ObstacleBlocks (block slots, chi, udef in the
     reference's layout, main.cpp:7256-7263) and the rigid motion (centre of mass, translation and angular velocity)."""
 
-    def __init__(self, slots, chi, udef, cm, vel, omega):
+    def __init__(self, slots, chi, udef, cm, vel, omega, *, forced=(0, 0, 0), block_rotation=(0, 0, 0), vel_imposed=(0, 0, 0)):
+        """forced / block_rotation / vel_imposed: Obstacle::bForcedInSimFrame, bBlockRotation and transVel_imposed, read by UpdateObstacles."""
         self.slots = np.ascontiguousarray(slots, dtype=np.int32)
         self.chi = np.ascontiguousarray(chi, dtype=np.float64).reshape(len(self.slots), 8, 8, 8)
         self.udef = np.ascontiguousarray(udef, dtype=np.float64).reshape(len(self.slots), 8, 8, 8, 3)
         self.cm, self.vel, self.omega = (np.array(v, dtype=np.float64) for v in (cm, vel, omega))
         self.force, self.torque = np.zeros(3), np.zeros(3)
+        self.forced, self.block_rotation = (tuple(int(bool(v)) for v in f) for f in (forced, block_rotation))
+        self.vel_imposed = np.array(vel_imposed, dtype=np.float64)
+        # what UpdateObstacles leaves: transVel_computed / angVel_computed, M (29 totals) and the blocks' 29 sums
+        self.vel_computed, self.omega_computed, self.totals, self.block_sums = None, None, None, None
 
 
 def _obstacle_array(obstacles):
@@ -502,6 +507,31 @@ def _obstacle_array(obstacles):
         for d in range(3):
             a.cm[d], a.vel[d], a.omega[d] = o.cm[d], o.vel[d], o.omega[d]
     return arr
+
+
+class UpdateObstacles(Operator):
+    """UpdateObstacles::operator()(dt), main.cpp:13812-13837, for sim.obstacles (ObstacleData list): KernelIntegrateFluidMomenta on the
+    resident vel, then kernelFinalizeObstacleVel and Obstacle::computeVelocities without the collision override (cup3d_update_obstacles).
+    Leaves in each ObstacleData the new vel / omega (what Penalization then penalises towards), vel_computed / omega_computed, totals
+    (M[29]) and block_sums [n][29].  A collective where the grid is spread over ranks."""
+
+    def __call__(self, dt):
+        s = self.sim
+        if not s.obstacles:
+            return
+        implicit = 1 if s.bImplicitPenalization else 0
+        arr = _obstacle_array(s.obstacles)
+        mot = (capi.ObstacleMotion * len(s.obstacles))()
+        sums = [np.zeros((len(o.slots), 29)) for o in s.obstacles]
+        for o, m, b in zip(s.obstacles, mot, sums):
+            for d in range(3):
+                m.forced[d], m.block_rotation[d], m.vel_imposed[d] = o.forced[d], o.block_rotation[d], o.vel_imposed[d]
+            m.block_sums = b.ctypes.data
+        check(lib().cup3d_update_obstacles(s.handle, dt, s.lambda_penal, implicit, len(s.obstacles), arr, mot))
+        for o, a, m, b in zip(s.obstacles, arr, mot, sums):
+            o.vel, o.omega = np.array(a.vel[:]), np.array(a.omega[:])
+            o.vel_computed, o.omega_computed = np.array(m.vel_computed[:]), np.array(m.omega_computed[:])
+            o.totals, o.block_sums = np.array(m.totals[:]), b
 
 
 class Penalization(Operator):
@@ -678,11 +708,15 @@ class Simulation:
     """The time loop of struct Simulation restricted to the hot path (no obstacles, frozen mesh):
     calcMaxTimestep 15254-15305, advance 15306-15326, pipeline order of setupOperators 15229-15246."""
 
-    def __init__(self, sim):
-        self.sim = sim
+    def __init__(self, sim, obstacle_operators=False):
+        """obstacle_operators: with sim.obstacles, put UpdateObstacles and Penalization between the forcing and PressureProjection
+        (15235-15243) -- the resident obstacle step.  Off by default: the caller then runs Penalization itself."""
+        self.sim, self.obstacle_operators = sim, bool(obstacle_operators)
         self.pipeline = [AdvectionDiffusionImplicit(sim) if sim.implicitDiffusion else AdvectionDiffusion(sim)]  # 15231-15234
         if sim.uMax_forced > 0:
             self.pipeline.append(ExternalForcing(sim))
+        if self.obstacle_operators and sim.obstacles:
+            self.pipeline += [UpdateObstacles(sim), Penalization(sim)]
         self.pipeline.append(PressureProjection(sim))
 
     def adaptMesh(self, Rtol, Ctol):
@@ -695,7 +729,7 @@ class Simulation:
             GradChiOnTmp(s)(0)
         st = s.grid.valid_states(MeshAdaptation(Rtol, Ctol).Tag(s, "tmpV"))
         if (st != 0).any():
-            self.__init__(s.adapted(st))
+            self.__init__(s.adapted(st), self.obstacle_operators)
         return st
 
     def adaptMeshOverRanks(self, mesh, owner, rank, nranks, Rtol, Ctol, allgather):
@@ -717,7 +751,7 @@ class Simulation:
         if not (st != 0).any():
             return st, mesh, owner
         new, new_mesh, new_owner = s.adapted_over_ranks(mesh, owner, st, rank, nranks)
-        self.__init__(new)
+        self.__init__(new, self.obstacle_operators)
         return st, new_mesh, new_owner
 
     def calcMaxTimestep(self):

@@ -350,6 +350,40 @@ CUP3D_API int cup3d_penalization(cup3d_sim_t *, double dt, double lambda, int im
 /* kernelUpdateTmpV (14948-14979): tmpV += udef where chi <= the obstacle's chi; call after clearing tmpV and before
  * cup3d_pressure_rhs / cup3d_pressure_project (15066-15085) */
 CUP3D_API int cup3d_update_tmpv(cup3d_sim_t *, int nobstacles, const cup3d_obstacle *obstacles);
+/* UpdateObstacles::operator() (13812-13837): the operator between the forcing and Penalization (setupOperators 15229-15246) that turns
+ * the freshly advected velocity inside an obstacle into the obstacle's translation and angular velocity -- the two that
+ * cup3d_penalization takes.  Per obstacle, obstacles one after the other (13739):
+ *   KernelIntegrateFluidMomenta<0/1>::visit (13637-13734) on the device from the resident vel and the staged chi / udef: per ObstacleBlock
+ *     the 29 sums in the order kernelFinalizeObstacleVel packs M (13748-13777) -- V, FX FY FZ, TX TY TZ, J0..J5, then GfX, GpX GpY GpZ,
+ *     Gj0..Gj5, GuX GuY GuZ, GaX GaY GaZ -- cells added in iz, iy, ix order, those with chi <= 0 skipped, in the reference's association:
+ *     bit for bit what the reference leaves in the ObstacleBlock.  Without implicit_penalization only the first 13 are computed.
+ *   one download of [nblocks][29] doubles (counted in cup3d_run_stats.field_bytes_downloaded) instead of the blocks' velocity;
+ *   kernelFinalizeObstacleVel (13737-13811) on the host: the block rows added in ascending slot order whatever order `slots` has (the
+ *     reference's loop with one thread), the all-reduce over ranks (13783), penalM / penalCM / penalJ / penalLmom / penalAmom by the two
+ *     branches of 13796-13808;
+ *   Obstacle::computeVelocities (12921-13068) on the host: the 6 x 6 matrix as written there, the bForcedInSimFrame / bBlockRotation row
+ *     edits, a dense LU with partial pivoting of this library's own (no GSL).
+ * On return obstacles[k].vel / omega hold the new transVel / angVel -- forced components equal vel_imposed, blocked rotations are 0,
+ * everything else is the computed value (13039-13068) -- and the same array goes straight into cup3d_penalization.  vel is only read.
+ * LEFT TO THE HOST: the force / torque of 13030-13038 (Penalization overwrites them), bBreakSymmetry's edit of transVel_imposed
+ * (12961-12966: pass the edited value), the collision override (13069 ff.), and the asserts on mass and J (13788-13794).
+ * COLLECTIVE like cup3d_penalization: every rank calls it with the same nobstacles; a rank that holds none of an obstacle's blocks passes
+ * nblocks = 0.  Per obstacle the 29 totals and an error flag cross the ranks as two all-reduces of at most 16 values from a device buffer
+ * of the call's own: a rank whose own arguments fail returns its own code, the others CUP3D_ECOMM, and every rank returns.
+ * CUP3D_EINVAL, nothing touched (neither motion[] nor obstacles[k].vel / omega, of any obstacle of the call): a null handle, dt <= 0,
+ * nobstacles < 0, null obstacles or motion with nobstacles > 0, nblocks < 0, a null array with nblocks > 0, a slot outside [0, nblocks of
+ * the sim), and -- after the all-reduce, so on every rank alike -- a total volume totals[0] <= DBL_EPSILON (the reference's
+ * assert(M[0] > EPS), 13795).  nobstacles = 0 is a no-op. */
+typedef struct {
+  int forced[3];           /* Obstacle::bForcedInSimFrame */
+  int block_rotation[3];   /* Obstacle::bBlockRotation */
+  double vel_imposed[3];   /* Obstacle::transVel_imposed */
+  double *block_sums;      /* out, may be NULL: [nblocks][29], order above; columns 13..28 written only with implicit_penalization */
+  double totals[29];       /* out: M after the sum over blocks and ranks (13783); 13..28 are 0 without implicit_penalization */
+  double vel_computed[3], omega_computed[3];   /* out: transVel_computed / angVel_computed (13022-13027) */
+} cup3d_obstacle_motion;
+CUP3D_API int cup3d_update_obstacles(cup3d_sim_t *, double dt, double lambda, int implicit_penalization, int nobstacles,
+                                     cup3d_obstacle *obstacles, cup3d_obstacle_motion *motion);
 /* ComputeForces::operator() without Obstacle::computeForces (main.cpp:12496-12503): KernelComputeForces::visit (12273-12493) on the
  * device.  One cup3d_obstacle_surface = the ObstacleBlocks of one Obstacle on this rank that have surface points (nPoints > 0; 12280
  * skips the others) with their surface_data as a CSR list: block i owns points [first[i], first[i+1]), ijk = surface_data::ix, iy, iz,

@@ -72,6 +72,14 @@ class ObstacleSurface(C.Structure):
                 ("cm", C.c_double * 3), ("vel", C.c_double * 3), ("omega", C.c_double * 3), ("points", C.c_void_p), ("qoi", C.c_void_p)]
 
 
+class ObstacleShape(C.Structure):
+    """cup3d_obstacle_shape"""
+    _fields_ = [("nblocks", C.c_long), ("slots", C.c_void_p), ("sdf", C.c_void_p), ("udef", C.c_void_p), ("chi", C.c_void_p),
+                ("transvel_correction", C.c_double * 3), ("angvel_correction", C.c_double * 3), ("cm", C.c_double * 3), ("mass", C.c_double),
+                ("J", C.c_double * 6), ("com_totals", C.c_double * 4), ("udef_totals", C.c_double * 13), ("block_com", C.c_void_p),
+                ("block_momenta", C.c_void_p), ("first", C.c_void_p), ("ijk", C.c_void_p), ("dchi", C.c_void_p), ("delta", C.c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/cup3d_hip.h
 SIGNATURES = {
     "cup3d_last_error": (C.c_char_p, []),
@@ -159,6 +167,7 @@ SIGNATURES = {
     "cup3d_penalization": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Obstacle)]),
     "cup3d_update_tmpv": (C.c_int, [_vp, C.c_int, C.POINTER(Obstacle)]),
     "cup3d_update_obstacles": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Obstacle), C.POINTER(ObstacleMotion)]),
+    "cup3d_create_obstacles": (C.c_int, [_vp, C.c_int, C.POINTER(ObstacleShape)]),
     "cup3d_compute_forces": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_compute_forces_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_profile_enable": (C.c_int, [C.c_int]),

@@ -1,7 +1,8 @@
 // Obstacle operators that sit between / inside the two hot-path operators: KernelPenalization
-// (main.cpp:13841-13912) + kernelFinalizePenalizationForce (13913-13938), kernelUpdateTmpV (14948-14979), UpdateObstacles (13812-13837)
-// and ComputeForces (12273-12503).
-// The obstacles themselves (geometry, chi/udef rasterisation, rigid-body integration) stay on the host; these kernels take the
+// (main.cpp:13841-13912) + kernelFinalizePenalizationForce (13913-13938), kernelUpdateTmpV (14948-14979), UpdateObstacles (13812-13837),
+// ComputeForces (12273-12503) and the grid half of CreateObstacles (13596-13619).
+// The obstacles themselves (geometry -- the signed distance and the deformation velocity -- and rigid-body integration) stay on the host;
+// cup3d_create_obstacles turns the signed distance into chi, surface points and momentum-free udef, and the other kernels take the
 // ObstacleBlocks of one obstacle at a time -- chi[8][8][8] and udef[8][8][8][3] in the reference's own (AoS) layout -- so the
 // velocity does not have to leave HBM between AdvectionDiffusion and PressureProjection when obstacles are present.
 // Velocities and tmpV are bit-exact with the reference; the penalisation force / torque sums are reductions (block totals summed in block
@@ -10,6 +11,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "sim.hpp"
@@ -835,5 +837,432 @@ extern "C" int cup3d_compute_forces_over_ranks(cup3d_sim_t *h, const cup3d_grid_
     if (nblocks && (rc = surface_download(s, o))) return rc;
   }
   if (bad) { set_error("%s", bad_text.c_str()); return bad; }
+  return CUP3D_OK;
+}
+
+// ==== cup3d_create_obstacles.  The grid half of CreateObstacles::operator() (main.cpp:13596-13619): the chi field cleared,
+// KernelCharacteristicFunction::operate (13298-13403), kernelComputeGridCoM (13406-13425), _kernelIntegrateUdefMomenta (13426-13488),
+// kernelAccumulateUdefMomenta (13495-13550) and kernelRemoveUdefMomenta (13551-13588) from the signed distance the obstacle's geometry
+// left in ObstacleBlock::sdfLab.  The staging is per call, as in cup3d_penalization.
+// One wavefront per ObstacleBlock in the two kernels that sum.  k_characteristic keeps sdfLab (8 000 B) and the block's chi (4 096 B) in
+// LDS; per z-plane every lane evaluates one cell, leaves its four summands in LDS and lanes 0..3 add them in cell order (ALL cells: the
+// reference skips none here).  The second loop then takes each plane again: a ballot of the accepted cells and a running count give
+// every surface point the place push_back gives it -- z, y, x order -- in the block's own stretch of a staging array, and k_pack_surface
+// moves the stretches to their CSR places once the host has turned the counts into `first`.  k_udef_momenta is k_fluid_momenta's pattern
+// with the thirteen terms of 13473-13485 in THEIR association (X * UDEF * dv, X * (..) * dv, X * p0 * p1 * dv), which is not
+// k_fluid_momenta's (X * dv * ..).
+namespace cup3d {
+
+constexpr int kUdefMomenta = 13;  // V, FX FY FZ, TX TY TZ, J0..J5 (kernelAccumulateUdefMomenta's M, 13504-13516)
+constexpr unsigned kUdefMomentaSubtracted = (1u << 10) | (1u << 11) | (1u << 12);  // J3 J4 J5 are accumulated with -= (13481-13485)
+
+struct ShapeItems {
+  const int32_t *slots;  // [n]
+  const double *geom;    // [n][4]: h, origin[3]
+  const double *sdf;     // [n][10][10][10]
+  double *udef;          // [n][512][3]
+  double *chi;           // [n][512]
+  double *com;           // [n][4]: mass, CoM_x, CoM_y, CoM_z
+  double *momenta;       // [n][13]
+  int32_t *count;        // [n] nPoints
+  int32_t *ijk;          // [n][512][3]  each block's points from the start of its own stretch
+  double *dchi;          // [n][512][3]
+  double *delta;         // [n][512]
+};
+
+__global__ void __launch_bounds__(64) k_characteristic(ShapeItems it, double *__restrict__ chi_field) {
+  __shared__ double sdf[1000];
+  __shared__ double chi[512];
+  __shared__ double sm[4][65];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int slot = it.slots[b];
+  for (int i = lane; i < 1000; i += 64) sdf[i] = it.sdf[(size_t)b * 1000 + i];
+  __syncthreads();
+  const double EPS = DBL_EPSILON;
+  const double h = it.geom[4 * b], inv2h = .5 / h, fac1 = .5 * h * h, vol = h * h * h;  // 13299
+  const int gp = 1;
+  const int x = lane & 7, y = lane >> 3;
+  auto S = [&](int k, int j, int i) { return sdf[((k + 1) * 10 + (j + 1)) * 10 + (i + 1)]; };
+  auto X = [&](int k, int j, int i) { return chi[(k * 8 + j) * 8 + i]; };
+  double total = 0.0;  // lanes 0..3: mass, CoM_x, CoM_y, CoM_z
+  for (int z = 0; z < 8; ++z) {
+    const double d = S(z, y, x);
+    double CHI;
+    if (d > +gp * h || d < -gp * h) {
+      CHI = d > 0 ? 1 : 0;
+    } else {
+      const double distPx = S(z, y, x + 1), distMx = S(z, y, x - 1);
+      const double distPy = S(z, y + 1, x), distMy = S(z, y - 1, x);
+      const double distPz = S(z + 1, y, x), distMz = S(z - 1, y, x);
+      const double gradUX = inv2h * (distPx - distMx);
+      const double gradUY = inv2h * (distPy - distMy);
+      const double gradUZ = inv2h * (distPz - distMz);
+      const double gradUSq = gradUX * gradUX + gradUY * gradUY + gradUZ * gradUZ + EPS;
+      // std::max((Real)0.0, dist): the first operand unless it is smaller
+      const double IplusX = 0.0 < distPx ? distPx : 0.0, IminuX = 0.0 < distMx ? distMx : 0.0;
+      const double IplusY = 0.0 < distPy ? distPy : 0.0, IminuY = 0.0 < distMy ? distMy : 0.0;
+      const double IplusZ = 0.0 < distPz ? distPz : 0.0, IminuZ = 0.0 < distMz ? distMz : 0.0;
+      const double gradIX = inv2h * (IplusX - IminuX);
+      const double gradIY = inv2h * (IplusY - IminuY);
+      const double gradIZ = inv2h * (IplusZ - IminuZ);
+      const double numH = gradIX * gradUX + gradIY * gradUY + gradIZ * gradUZ;
+      CHI = numH / gradUSq;
+    }
+    const int c = z * 64 + lane;
+    chi[c] = CHI;
+    it.chi[(size_t)b * 512 + c] = CHI;
+    const double p0 = it.geom[4 * b + 1] + h * (x + 0.5), p1 = it.geom[4 * b + 2] + h * (y + 0.5), p2 = it.geom[4 * b + 3] + h * (z + 0.5);
+    const double r = chi_field[(size_t)slot * 512 + c];
+    chi_field[(size_t)slot * 512 + c] = CHI < r ? r : CHI;  // std::max(CHI, b.s), 13349
+    sm[0][lane] = CHI * vol;
+    sm[1][lane] = CHI * vol * p0;
+    sm[2][lane] = CHI * vol * p1;
+    sm[3][lane] = CHI * vol * p2;
+    __syncthreads();
+    if (lane < 4)
+      for (int j = 0; j < 64; ++j) total += sm[lane][j];
+    __syncthreads();
+  }
+  if (lane < 4) it.com[(size_t)b * 4 + lane] = total;
+  int npoints = 0;  // the same in every lane
+  for (int z = 0; z < 8; ++z) {  // 13355-13400
+    const double gradUX = inv2h * (S(z, y, x + 1) - S(z, y, x - 1));
+    const double gradUY = inv2h * (S(z, y + 1, x) - S(z, y - 1, x));
+    const double gradUZ = inv2h * (S(z + 1, y, x) - S(z - 1, y, x));
+    const double gradUSq = gradUX * gradUX + gradUY * gradUY + gradUZ * gradUZ + EPS;
+    const double gradHX = (x == 0) ? 2.0 * (-0.5 * X(z, y, x + 2) + 2.0 * X(z, y, x + 1) - 1.5 * X(z, y, x))
+                                   : ((x == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z, y, x - 1) + 0.5 * X(z, y, x - 2)) : (X(z, y, x + 1) - X(z, y, x - 1)));
+    const double gradHY = (y == 0) ? 2.0 * (-0.5 * X(z, y + 2, x) + 2.0 * X(z, y + 1, x) - 1.5 * X(z, y, x))
+                                   : ((y == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z, y - 1, x) + 0.5 * X(z, y - 2, x)) : (X(z, y + 1, x) - X(z, y - 1, x)));
+    const double gradHZ = (z == 0) ? 2.0 * (-0.5 * X(z + 2, y, x) + 2.0 * X(z + 1, y, x) - 1.5 * X(z, y, x))
+                                   : ((z == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z - 1, y, x) + 0.5 * X(z - 2, y, x)) : (X(z + 1, y, x) - X(z - 1, y, x)));
+    bool accepted = false;
+    double Delta = 0.0;
+    if (!(gradHX * gradHX + gradHY * gradHY + gradHZ * gradHZ < 1e-12)) {
+      const double numD = gradHX * gradUX + gradHY * gradUY + gradHZ * gradUZ;
+      Delta = fac1 * numD / gradUSq;
+      accepted = Delta > EPS;
+    }
+    const unsigned long long mask = __ballot(accepted);
+    if (accepted) {  // ObstacleBlock::write (7422-7431)
+      const size_t at = (size_t)b * 512 + npoints + __popcll(mask & ((1ull << lane) - 1ull));  // < 512: one place per cell at most
+      it.ijk[3 * at] = x;
+      it.ijk[3 * at + 1] = y;
+      it.ijk[3 * at + 2] = z;
+      it.dchi[3 * at] = -Delta * gradUX;
+      it.dchi[3 * at + 1] = -Delta * gradUY;
+      it.dchi[3 * at + 2] = -Delta * gradUZ;
+      it.delta[at] = Delta;
+    }
+    npoints += __popcll(mask);
+  }
+  if (lane == 0) it.count[b] = npoints;
+}
+
+// block b's points: from its stretch of the staging arrays to [first[b], first[b+1]) of the CSR arrays
+__global__ void __launch_bounds__(64) k_pack_surface(ShapeItems it, const int32_t *__restrict__ first, int32_t *__restrict__ ijk, double *__restrict__ dchi,
+                                                      double *__restrict__ delta) {
+  const int b = blockIdx.x;
+  const int p0 = first[b], n = first[b + 1] - p0;
+  for (int i = threadIdx.x; i < n; i += 64) {
+    const size_t from = (size_t)b * 512 + i, to = (size_t)p0 + i;
+    for (int d = 0; d < 3; ++d) {
+      ijk[3 * to + d] = it.ijk[3 * from + d];
+      dchi[3 * to + d] = it.dchi[3 * from + d];
+    }
+    delta[to] = it.delta[from];
+  }
+}
+
+__global__ void __launch_bounds__(64) k_udef_momenta(ShapeItems it, double cm0, double cm1, double cm2, double oc0, double oc1, double oc2) {
+  __shared__ double sm[kUdefMomenta][65];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const double h = it.geom[4 * b], dv = h * h * h;  // 13466
+  const int ix = lane & 7, iy = lane >> 3;
+  const bool subtracted = (kUdefMomentaSubtracted >> lane) & 1u;
+  double total = 0.0;  // lanes 0..12: the running sum of quantity `lane`
+  for (int iz = 0; iz < 8; ++iz) {
+    const int c = iz * 64 + lane;
+    const double X = it.chi[(size_t)b * 512 + c];
+    const bool visited = !(X <= 0);  // `if (CHI[z][y][x] <= 0) continue;`
+    const unsigned long long mask = __ballot(visited);
+    if (visited) {
+      double p[3] = {it.geom[4 * b + 1] + h * (ix + 0.5), it.geom[4 * b + 2] + h * (iy + 0.5), it.geom[4 * b + 3] + h * (iz + 0.5)};
+      p[0] -= cm0; p[1] -= cm1; p[2] -= cm2;
+      const double *U = it.udef + ((size_t)b * 512 + c) * 3;
+      const double U0 = U[0], U1 = U[1], U2 = U[2];
+      const double dUs = U0 - oc0, dVs = U1 - oc1, dWs = U2 - oc2;
+      sm[0][lane] = X * dv;
+      sm[1][lane] = X * U0 * dv;
+      sm[2][lane] = X * U1 * dv;
+      sm[3][lane] = X * U2 * dv;
+      sm[4][lane] = X * (p[1] * dWs - p[2] * dVs) * dv;
+      sm[5][lane] = X * (p[2] * dUs - p[0] * dWs) * dv;
+      sm[6][lane] = X * (p[0] * dVs - p[1] * dUs) * dv;
+      sm[7][lane] = X * (p[1] * p[1] + p[2] * p[2]) * dv;
+      sm[8][lane] = X * (p[0] * p[0] + p[2] * p[2]) * dv;
+      sm[9][lane] = X * (p[0] * p[0] + p[1] * p[1]) * dv;
+      sm[10][lane] = X * p[0] * p[1] * dv;
+      sm[11][lane] = X * p[0] * p[2] * dv;
+      sm[12][lane] = X * p[1] * p[2] * dv;
+    }
+    __syncthreads();
+    if (lane < kUdefMomenta) {
+      for (int j = 0; j < 64; ++j)
+        if ((mask >> j) & 1ull) {
+          const double x = sm[lane][j];
+          total = subtracted ? total - x : total + x;
+        }
+    }
+    __syncthreads();
+  }
+  if (lane < kUdefMomenta) it.momenta[(size_t)b * kUdefMomenta + lane] = total;
+}
+
+__global__ void __launch_bounds__(256) k_remove_udef_momenta(ShapeItems it, double cm0, double cm1, double cm2, double t0, double t1, double t2, double a0,
+                                                              double a1, double a2) {
+  const int b = blockIdx.x, t = threadIdx.x;
+  const double h = it.geom[4 * b];
+  for (int k = 0; k < 2; ++k) {
+    const int c = k * 256 + t, ix = c & 7, iy = (c >> 3) & 7, iz = c >> 6;
+    double p[3] = {it.geom[4 * b + 1] + h * (ix + 0.5), it.geom[4 * b + 2] + h * (iy + 0.5), it.geom[4 * b + 3] + h * (iz + 0.5)};
+    p[0] -= cm0; p[1] -= cm1; p[2] -= cm2;
+    const double rot0 = a1 * p[2] - a2 * p[1], rot1 = a2 * p[0] - a0 * p[2], rot2 = a0 * p[1] - a1 * p[0];  // 13578-13581
+    double *U = it.udef + ((size_t)b * 512 + c) * 3;
+    U[0] = U[0] - (t0 + rot0);
+    U[1] = U[1] - (t1 + rot1);
+    U[2] = U[2] - (t2 + rot2);
+  }
+}
+
+namespace {
+// invertSym (9092-9105)
+void invert_sym(const double *J, double *inv) {
+  const double detJ = J[0] * (J[1] * J[2] - J[5] * J[5]) + J[3] * (J[4] * J[5] - J[2] * J[3]) + J[4] * (J[3] * J[5] - J[1] * J[4]);
+  if (std::fabs(detJ) <= DBL_MIN) {
+    for (int q = 0; q < 6; ++q) inv[q] = 0.0;
+    return;
+  }
+  inv[0] = (J[1] * J[2] - J[5] * J[5]) / detJ;
+  inv[1] = (J[0] * J[2] - J[4] * J[4]) / detJ;
+  inv[2] = (J[0] * J[1] - J[3] * J[3]) / detJ;
+  inv[3] = (J[4] * J[5] - J[2] * J[3]) / detJ;
+  inv[4] = (J[3] * J[5] - J[1] * J[4]) / detJ;
+  inv[5] = (J[3] * J[4] - J[0] * J[5]) / detJ;
+}
+
+int shape_check(const Sim *s, const cup3d_obstacle_shape &o, int k) {
+  if (o.nblocks < 0) { set_error("cup3d_create_obstacles: obstacle %d has nblocks = %ld", k, o.nblocks); return CUP3D_EINVAL; }
+  if (o.nblocks == 0) return CUP3D_OK;
+  if (!o.slots || !o.sdf || !o.udef || !o.chi || !o.first || !o.ijk || !o.dchi || !o.delta) {
+    set_error("cup3d_create_obstacles: obstacle %d has blocks but a null array", k);
+    return CUP3D_EINVAL;
+  }
+  for (long i = 0; i < o.nblocks; ++i)
+    if (o.slots[i] < 0 || o.slots[i] >= s->nb) { set_error("cup3d_create_obstacles: obstacle %d: block slot %d out of range", k, (int)o.slots[i]); return CUP3D_EINVAL; }
+  return CUP3D_OK;
+}
+
+// what one obstacle of a call leaves on the device and on the host until every obstacle of the call has passed
+struct ShapeWork {
+  DevBuf slots, geom, sdf, udef, chi, com, momenta, count, st_ijk, st_dchi, st_delta, first, ijk, dchi, delta;
+  ShapeItems it;
+  std::vector<double> com_rows, momenta_rows;
+  std::vector<int32_t> first_h;
+  double com_totals[4], M[kUdefMomenta], cm[3], transvel[3], angvel[3];
+};
+
+// rows [n][width] added in ascending slot order onto total[width]: the reference's loops over obstacleBlocks with one thread
+void add_rows_in_slot_order(const int32_t *slots, long n, const std::vector<double> &rows, int width, double *total) {
+  std::vector<long> order(n);
+  for (long i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return slots[a] < slots[b]; });
+  for (long i : order)
+    for (int q = 0; q < width; ++q) total[q] += rows[(size_t)i * width + q];
+}
+}  // namespace
+
+}  // namespace cup3d
+
+extern "C" int cup3d_create_obstacles(cup3d_sim_t *h, int nobst, cup3d_obstacle_shape *shapes) {
+  if (!h || nobst < 0 || (nobst > 0 && !shapes)) return CUP3D_EINVAL;
+  if (nobst == 0) return CUP3D_OK;  // 13590: nothing is cleared either
+  Sim *s = reinterpret_cast<Sim *>(h);
+  const bool cross = scalars_cross_ranks(s);
+  // nothing is written, on the device or the host, before every obstacle of the call has passed.  Over ranks a rank whose own arguments
+  // are refused still takes part in the first all-reduce, where its flag ends the call on every rank.
+  int bad = CUP3D_OK;
+  for (int k = 0; k < nobst && !bad; ++k) bad = shape_check(s, shapes[k], k);
+  if (bad && !cross) return bad;
+  const std::string bad_text = bad ? cup3d_last_error() : "";
+  DevBuf red;  // the all-reduce operand of this call: up to 13 totals and the error flag
+  int rc;
+  if (cross && (rc = red.alloc(16 * sizeof(double)))) return rc;
+  // v[n] summed over the ranks along with a flag -- 0, or 1 from a rank whose local part failed -- so that one rank's failure is an error
+  // everywhere and leaves no rank inside a collective (as in cup3d_update_obstacles); n <= 15
+  auto over_ranks = [&](double *v, int n, int local, int k) -> int {
+    if (!cross) return local;
+    double buf[16] = {0};
+    for (int q = 0; q < n; ++q) buf[q] = local ? 0.0 : v[q];
+    buf[n] = local ? 1.0 : 0.0;
+    double *d = (double *)red.p;
+    hipStream_t cs = scalar_stream(s);
+    int rc2;
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    CUP3D_HIP(hipMemcpyAsync(d, buf, 16 * sizeof(double), hipMemcpyHostToDevice, cs));
+    if ((rc2 = allreduce(s, d, n + 1, false, cs))) return local ? local : rc2;
+    CUP3D_HIP(hipMemcpyAsync(buf, d, 16 * sizeof(double), hipMemcpyDeviceToHost, cs));
+    CUP3D_HIP(hipStreamSynchronize(cs));
+    for (int q = 0; q < n; ++q) v[q] = buf[q];
+    if (local) return local;
+    if (buf[n] != 0.0) {
+      set_error("cup3d_create_obstacles: obstacle %d failed on %d other rank(s)", k, (int)buf[n]);
+      return CUP3D_ECOMM;
+    }
+    return CUP3D_OK;
+  };
+  if (!bad) {  // CHI.clear() of every block (13596-13600)
+    CUP3D_HIP(hipMemsetAsync(s->chi, 0, (size_t)s->nb * 512 * sizeof(double), stream()));
+    s->chi_nonzero = true;
+  }
+  std::vector<ShapeWork> work((size_t)nobst);
+  for (int k = 0; k < nobst; ++k) {  // obstacles one after the other: the max into the chi field in the order 13301 visits them
+    const cup3d_obstacle_shape &o = shapes[k];
+    ShapeWork &W = work[k];
+    const long n = bad ? 0 : o.nblocks;
+    const size_t nb = (size_t)n;
+    for (int q = 0; q < 4; ++q) W.com_totals[q] = 0.0;
+    for (int q = 0; q < kUdefMomenta; ++q) W.M[q] = 0.0;
+    W.first_h.assign(nb + 1, 0);
+    auto characteristic = [&]() -> int {
+      if (bad) return bad;
+      if (n == 0) return CUP3D_OK;
+      const Grid *g = s->grid;
+      std::vector<double> gm(4 * nb);
+      for (size_t i = 0; i < nb; ++i) {
+        const int32_t b = o.slots[i];
+        const double hb = g->multilevel ? g->hb[b] : g->h;
+        gm[4 * i] = hb;
+        for (int d = 0; d < 3; ++d) gm[4 * i + 1 + d] = g->index[3 * (size_t)b + d] * kBS * hb;  // Info::origin, main.cpp:1066-1068
+      }
+      int rc;
+      if ((rc = W.slots.upload(o.slots, nb * sizeof(int32_t))) || (rc = W.geom.upload(gm.data(), gm.size() * sizeof(double))) ||
+          (rc = W.sdf.upload(o.sdf, nb * 1000 * sizeof(double))) || (rc = W.udef.upload(o.udef, nb * 1536 * sizeof(double))) ||
+          (rc = W.chi.alloc(nb * 512 * sizeof(double))) || (rc = W.com.alloc(nb * 4 * sizeof(double))) ||
+          (rc = W.momenta.alloc(nb * kUdefMomenta * sizeof(double))) || (rc = W.count.alloc(nb * sizeof(int32_t))) ||
+          (rc = W.st_ijk.alloc(nb * 1536 * sizeof(int32_t))) || (rc = W.st_dchi.alloc(nb * 1536 * sizeof(double))) ||
+          (rc = W.st_delta.alloc(nb * 512 * sizeof(double))))
+        return rc;
+      CUP3D_HIP(hipStreamSynchronize(stream()));  // gm is a local
+      W.it = ShapeItems{(const int32_t *)W.slots.p, (const double *)W.geom.p, (const double *)W.sdf.p, (double *)W.udef.p, (double *)W.chi.p, (double *)W.com.p,
+                        (double *)W.momenta.p, (int32_t *)W.count.p, (int32_t *)W.st_ijk.p, (double *)W.st_dchi.p, (double *)W.st_delta.p};
+      {
+        ProfileScope ps("characteristic");
+        hipLaunchKernelGGL(k_characteristic, dim3((unsigned)n), dim3(64), 0, stream(), W.it, s->chi);
+      }
+      CUP3D_HIP(hipGetLastError());
+      W.com_rows.resize(nb * 4);
+      std::vector<int32_t> count(nb);
+      CUP3D_HIP(hipMemcpyAsync(W.com_rows.data(), W.com.p, nb * 4 * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipMemcpyAsync(count.data(), W.count.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipStreamSynchronize(stream()));
+      stats_field_download(nb * (4 * sizeof(double) + sizeof(int32_t)));
+      for (size_t i = 0; i < nb; ++i) {
+        if (count[i] < 0 || count[i] > 512) { set_error("cup3d_create_obstacles: obstacle %d: block %ld reports %d surface points", k, (long)i, (int)count[i]); return CUP3D_ESTATE; }
+        W.first_h[i + 1] = W.first_h[i] + count[i];
+      }
+      const size_t np = (size_t)W.first_h[nb];
+      if ((rc = W.first.upload(W.first_h.data(), (nb + 1) * sizeof(int32_t))) || (rc = W.ijk.alloc(np * 3 * sizeof(int32_t))) ||
+          (rc = W.dchi.alloc(np * 3 * sizeof(double))) || (rc = W.delta.alloc(np * sizeof(double))))
+        return rc;
+      {
+        ProfileScope ps("pack_surface");
+        hipLaunchKernelGGL(k_pack_surface, dim3((unsigned)n), dim3(64), 0, stream(), W.it, (const int32_t *)W.first.p, (int32_t *)W.ijk.p, (double *)W.dchi.p,
+                           (double *)W.delta.p);
+      }
+      CUP3D_HIP(hipGetLastError());
+      add_rows_in_slot_order(o.slots, n, W.com_rows, 4, W.com_totals);  // kernelComputeGridCoM, 13411-13418
+      return CUP3D_OK;
+    };
+    rc = over_ranks(W.com_totals, 4, characteristic(), k);  // MPI_Allreduce(com, 4), 13419
+    if (rc) {
+      if (bad) set_error("%s", bad_text.c_str());
+      return rc;
+    }
+    if (!(W.com_totals[0] > DBL_EPSILON)) {  // assert(com[0] > epsilon), 13420: the same total on every rank
+      set_error("cup3d_create_obstacles: obstacle %d has volume %g", k, W.com_totals[0]);
+      return CUP3D_EINVAL;
+    }
+    for (int d = 0; d < 3; ++d) {
+      W.cm[d] = W.com_totals[1 + d] / W.com_totals[0];
+      W.transvel[d] = o.transvel_correction[d];  // oldCorrVel, 13436
+    }
+    auto momenta = [&]() -> int {
+      if (n == 0) return CUP3D_OK;
+      {
+        ProfileScope ps("udef_momenta");
+        hipLaunchKernelGGL(k_udef_momenta, dim3((unsigned)n), dim3(64), 0, stream(), W.it, W.cm[0], W.cm[1], W.cm[2], W.transvel[0], W.transvel[1], W.transvel[2]);
+      }
+      CUP3D_HIP(hipGetLastError());
+      W.momenta_rows.resize(nb * kUdefMomenta);
+      CUP3D_HIP(hipMemcpyAsync(W.momenta_rows.data(), W.momenta.p, W.momenta_rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipStreamSynchronize(stream()));
+      stats_field_download(W.momenta_rows.size() * sizeof(double));
+      add_rows_in_slot_order(o.slots, n, W.momenta_rows, kUdefMomenta, W.M);  // 13501-13517
+      return CUP3D_OK;
+    };
+    if ((rc = over_ranks(W.M, kUdefMomenta, momenta(), k))) return rc;  // MPI_Allreduce(M, 13), 13519
+    if (!(W.M[0] > DBL_EPSILON)) {  // assert(M[0] > EPS), 13520
+      set_error("cup3d_create_obstacles: obstacle %d has volume %g under chi > 0", k, W.M[0]);
+      return CUP3D_EINVAL;
+    }
+    double invJ[6];
+    invert_sym(W.M + 7, invJ);
+    const double *AM = W.M + 4;
+    for (int d = 0; d < 3; ++d) W.transvel[d] = W.M[1 + d] / W.M[0];  // 13533-13535
+    W.angvel[0] = invJ[0] * AM[0] + invJ[3] * AM[1] + invJ[4] * AM[2];  // 13542-13547
+    W.angvel[1] = invJ[3] * AM[0] + invJ[1] * AM[1] + invJ[5] * AM[2];
+    W.angvel[2] = invJ[4] * AM[0] + invJ[5] * AM[1] + invJ[2] * AM[2];
+    if (n > 0) {
+      ProfileScope ps("remove_udef_momenta");
+      hipLaunchKernelGGL(k_remove_udef_momenta, dim3((unsigned)n), dim3(256), 0, stream(), W.it, W.cm[0], W.cm[1], W.cm[2], W.transvel[0], W.transvel[1],
+                         W.transvel[2], W.angvel[0], W.angvel[1], W.angvel[2]);
+      CUP3D_HIP(hipGetLastError());
+    }
+  }
+  // every obstacle has passed: the caller's arrays
+  for (int k = 0; k < nobst; ++k) {
+    cup3d_obstacle_shape &o = shapes[k];
+    ShapeWork &W = work[k];
+    const size_t nb = (size_t)o.nblocks, np = (size_t)W.first_h[nb];
+    if (nb) {
+      CUP3D_HIP(hipMemcpyAsync(o.chi, W.chi.p, nb * 512 * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipMemcpyAsync(o.udef, W.udef.p, nb * 1536 * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      if (np) {
+        CUP3D_HIP(hipMemcpyAsync(o.ijk, W.ijk.p, np * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
+        CUP3D_HIP(hipMemcpyAsync(o.dchi, W.dchi.p, np * 3 * sizeof(double), hipMemcpyDeviceToHost, stream()));
+        CUP3D_HIP(hipMemcpyAsync(o.delta, W.delta.p, np * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      }
+      CUP3D_HIP(hipStreamSynchronize(stream()));
+      stats_field_download(nb * 2048 * sizeof(double) + np * (3 * sizeof(int32_t) + 4 * sizeof(double)));
+      for (size_t i = 0; i <= nb; ++i) o.first[i] = W.first_h[i];
+      if (o.block_com)
+        for (size_t i = 0; i < nb * 4; ++i) o.block_com[i] = W.com_rows[i];
+      if (o.block_momenta)
+        for (size_t i = 0; i < nb * kUdefMomenta; ++i) o.block_momenta[i] = W.momenta_rows[i];
+    } else if (o.first) {
+      o.first[0] = 0;
+    }
+    for (int q = 0; q < 4; ++q) o.com_totals[q] = W.com_totals[q];
+    for (int q = 0; q < kUdefMomenta; ++q) o.udef_totals[q] = W.M[q];
+    o.mass = W.M[0];  // 13532
+    for (int q = 0; q < 6; ++q) o.J[q] = W.M[7 + q];  // 13536-13541
+    for (int d = 0; d < 3; ++d) {
+      o.cm[d] = W.cm[d];
+      o.transvel_correction[d] = W.transvel[d];
+      o.angvel_correction[d] = W.angvel[d];
+    }
+  }
+  CUP3D_HIP(hipStreamSynchronize(stream()));
   return CUP3D_OK;
 }

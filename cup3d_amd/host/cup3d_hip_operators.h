@@ -581,6 +581,110 @@ public:
   }
 };
 
+// CreateObstacles::operator()(dt), main.cpp:13589-13621, with everything after obstacle_vector->create() on the device
+// (cup3d_create_obstacles): the geometry -- updateUinf, update, create, which leave sdfLab and udef in the ObstacleBlocks -- stays the
+// reference's, and so do the MeshChanged / StaticObstacles gate and finalize().  The blocks' chi, corrected udef, mass / CoM rows, the 13
+// momenta, the surface points and the obstacle's centre of mass, mass, J and corrections come back into the reference's own objects;
+// the chi field stays on the device and its obstacle blocks are copied into the host grid, which the call has cleared.
+// Installed only with CUP3D_HIP_CREATE=1 (install()).
+class CreateObstaclesHIP : public Operator {
+  std::shared_ptr<DeviceMirror> devp;
+  DeviceMirror &dev;
+
+public:
+  CreateObstaclesHIP(SimulationData &s, std::shared_ptr<DeviceMirror> d) : Operator(s), devp(d), dev(*d) {}
+  void operator()(const Real dt) override {
+    (void)dt;
+    if (sim.obstacle_vector->nObstacles() == 0) return;  // 13590-13591
+    if (sim.MeshChanged == false && sim.StaticObstacles) return;
+    sim.MeshChanged = false;
+    static_assert(sizeof(Real) == sizeof(double), "the device operators are FP64");
+    std::vector<Info> &chiInfo = sim.chiInfo();
+    for (size_t i = 0; i < chiInfo.size(); ++i) ((ScalarBlock *)chiInfo[i].block)->clear();  // 13596-13600: the host copy
+    sim.uinf = sim.obstacle_vector->updateUinf();
+    sim.obstacle_vector->update();
+    sim.obstacle_vector->create();
+    dev.handle();
+    const auto &obstacles = sim.obstacle_vector->getObstacleVector();
+    const size_t nobst = obstacles.size();
+    struct Packed {
+      std::vector<ObstacleBlock *> blocks;
+      std::vector<int32_t> slots, first, ijk;
+      std::vector<double> sdf, udef, chi, com, momenta, dchi, delta;
+    };
+    std::vector<Packed> packed(nobst);
+    std::vector<cup3d_obstacle_shape> shapes(nobst);
+    for (size_t k = 0; k < nobst; ++k) {
+      Packed &P = packed[k];
+      const std::vector<ObstacleBlock *> &ob = obstacles[k]->getObstacleBlocks();
+      for (size_t i = 0; i < chiInfo.size(); ++i) {  // block slot i of the mirror is m_vInfo entry i
+        ObstacleBlock *o = ob[chiInfo[i].blockID];
+        if (o == nullptr) continue;  // 13304-13305
+        P.blocks.push_back(o);
+        P.slots.push_back((int32_t)i);
+        const double *d = &o->sdfLab[0][0][0], *u = &o->udef[0][0][0][0];
+        P.sdf.insert(P.sdf.end(), d, d + 10 * 10 * 10);
+        P.udef.insert(P.udef.end(), u, u + 8 * 8 * 8 * 3);
+      }
+      const size_t n = P.blocks.size();
+      P.chi.resize(n * 512);
+      P.com.resize(n * 4);
+      P.momenta.resize(n * 13);
+      P.first.resize(n + 1);
+      P.ijk.resize(n * 512 * 3);
+      P.dchi.resize(n * 512 * 3);
+      P.delta.resize(n * 512);
+      cup3d_obstacle_shape &S = shapes[k];
+      S.nblocks = (long)n;
+      S.slots = P.slots.data();
+      S.sdf = P.sdf.data();
+      S.udef = P.udef.data();
+      S.chi = P.chi.data();
+      for (int d = 0; d < 3; ++d) S.transvel_correction[d] = obstacles[k]->transVel_correction[d];  // oldCorrVel, 13436
+      S.block_com = P.com.data();
+      S.block_momenta = P.momenta.data();
+      S.first = P.first.data();
+      S.ijk = P.ijk.data();
+      S.dchi = P.dchi.data();
+      S.delta = P.delta.data();
+    }
+    CUP3D_HIP_CALL(cup3d_create_obstacles(dev.handle(), (int)nobst, shapes.data()));
+    for (size_t k = 0; k < nobst; ++k) {
+      Packed &P = packed[k];
+      const cup3d_obstacle_shape &S = shapes[k];
+      for (size_t b = 0; b < P.blocks.size(); ++b) {
+        ObstacleBlock &o = *P.blocks[b];
+        std::copy(P.chi.begin() + b * 512, P.chi.begin() + (b + 1) * 512, &o.chi[0][0][0]);
+        std::copy(P.udef.begin() + b * 1536, P.udef.begin() + (b + 1) * 1536, &o.udef[0][0][0][0]);
+        o.mass = P.com[4 * b];  // 13307-13310, 13350-13353
+        o.CoM_x = P.com[4 * b + 1];
+        o.CoM_y = P.com[4 * b + 2];
+        o.CoM_z = P.com[4 * b + 3];
+        const double *m = &P.momenta[13 * b];  // 13441-13445
+        o.V = m[0];
+        o.FX = m[1]; o.FY = m[2]; o.FZ = m[3];
+        o.TX = m[4]; o.TY = m[5]; o.TZ = m[6];
+        o.J0 = m[7]; o.J1 = m[8]; o.J2 = m[9]; o.J3 = m[10]; o.J4 = m[11]; o.J5 = m[12];
+        for (int32_t p = P.first[b]; p < P.first[b + 1]; ++p) {  // ObstacleBlock::write (7422-7431) with dchi already formed
+          o.nPoints++;
+          o.surface.push_back(new surface_data(P.ijk[3 * p], P.ijk[3 * p + 1], P.ijk[3 * p + 2], P.dchi[3 * p], P.dchi[3 * p + 1], P.dchi[3 * p + 2], P.delta[p]));
+        }
+        o.allocate_surface();  // 13401
+      }
+      for (int d = 0; d < 3; ++d) {
+        obstacles[k]->centerOfMass[d] = S.cm[d];  // 13421-13423
+        obstacles[k]->transVel_correction[d] = S.transvel_correction[d];  // 13533-13535
+        obstacles[k]->angVel_correction[d] = S.angvel_correction[d];  // 13542-13547
+      }
+      obstacles[k]->mass = S.mass;  // 13532
+      for (int q = 0; q < 6; ++q) obstacles[k]->J[q] = S.J[q];  // 13536-13541
+    }
+    dev.download_obstacle_blocks(CUP3D_FIELD_CHI);  // the rest of the host's chi is the zero it was cleared to
+    dev.chi_uploaded_step = sim.step;
+    sim.obstacle_vector->finalize();  // 13620
+  }
+};
+
 // One DeviceMirror per SimulationData, shared by every HIP-backed operator / solver built for it.
 inline std::shared_ptr<DeviceMirror> mirror_of(SimulationData &sim) {
   static std::map<SimulationData *, std::weak_ptr<DeviceMirror>> reg;
@@ -604,6 +708,7 @@ struct Installed {
   std::shared_ptr<UpdateObstaclesHIP> update_obstacles;
   std::shared_ptr<PressureProjectionHIP> projection;
   std::shared_ptr<ComputeForcesHIP> forces;  // only with CUP3D_HIP_FORCES=1
+  std::shared_ptr<CreateObstaclesHIP> create_obstacles;  // only with CUP3D_HIP_CREATE=1
 };
 
 // Swap the hot-path operators of an initialised Simulation for the HIP-backed ones.
@@ -615,7 +720,7 @@ struct Installed {
 // PressureProjectionHIP sends them back); without obstacles both return immediately (13813-13814, 14327-14328).  With
 // FixMassFlux in between, every operator round-trips in full as before.
 // CUP3D_HIP_FORCES=1 (environment): ComputeForces (15244) is replaced by ComputeForcesHIP as well; without it that entry of the
-// pipeline stays the reference's own.
+// pipeline stays the reference's own.  CUP3D_HIP_CREATE=1: CreateObstacles (15230) is replaced by CreateObstaclesHIP in the same way.
 inline Installed install(SimulationData &sim, int resident = -1) {
   Installed r;
   r.mirror = mirror_of(sim);
@@ -637,10 +742,15 @@ inline Installed install(SimulationData &sim, int resident = -1) {
   const char *forces_env = getenv("CUP3D_HIP_FORCES");
   const bool forces = forces_env && atoi(forces_env) == 1;
   if (forces) r.mirror->keep_global_mesh = true;
+  const char *create_env = getenv("CUP3D_HIP_CREATE");
+  const bool create = create_env && atoi(create_env) == 1;
   for (auto &op : sim.pipeline) {
     if (forces && std::dynamic_pointer_cast<ComputeForces>(op)) {
       r.forces = std::make_shared<ComputeForcesHIP>(sim, r.mirror);
       op = r.forces;
+    } else if (create && std::dynamic_pointer_cast<CreateObstacles>(op)) {
+      r.create_obstacles = std::make_shared<CreateObstaclesHIP>(sim, r.mirror);
+      op = r.create_obstacles;
     } else if (std::dynamic_pointer_cast<AdvectionDiffusion>(op)) {
       r.advdiff = std::make_shared<AdvectionDiffusionHIP>(sim, r.mirror);
       op = r.advdiff;

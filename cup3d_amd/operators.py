@@ -509,6 +509,76 @@ def _obstacle_array(obstacles):
     return arr
 
 
+class ObstacleShape:
+    """What the host's geometry leaves of one obstacle on this rank (Obstacle::create): the non-null ObstacleBlocks' slots, their signed
+    distance sdf [n][10][10][10] (ObstacleBlock::sdfLab, index [z+1][y+1][x+1]) and deformation velocity udef [n][8][8][8][3], plus
+    Obstacle::transVel_correction as the previous step left it.  CreateObstacles fills the rest: chi [n][8][8][8], udef_corrected (udef with
+    kernelRemoveUdefMomenta applied; `udef` itself stays as the geometry wrote it), cm, mass, J, both corrections (transvel_correction is
+    replaced: the next call reads it as oldCorrVel), com_totals [4], udef_totals [13], block_com [n][4], block_momenta [n][13] and the
+    surface as a CSR list over the blocks in the order listed: first [n+1], ijk [np][3], dchi [np][3], delta [np]."""
+
+    def __init__(self, slots, sdf, udef, transvel_correction=(0, 0, 0)):
+        self.slots = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        n = len(self.slots)
+        self.sdf = np.ascontiguousarray(sdf, dtype=np.float64).reshape(n, 10, 10, 10)
+        self.udef = np.ascontiguousarray(udef, dtype=np.float64).reshape(n, 8, 8, 8, 3)
+        self.transvel_correction = np.array(transvel_correction, dtype=np.float64)
+        self.chi = self.udef_corrected = self.cm = self.mass = self.J = self.angvel_correction = None
+        self.com_totals = self.udef_totals = self.block_com = self.block_momenta = self.first = self.ijk = self.dchi = self.delta = None
+
+    def data(self, vel, omega, **kw):
+        """The ObstacleData of this obstacle for UpdateObstacles / Penalization / PressureProjection: slots, chi, the corrected udef and
+        the centre of mass as CreateObstacles left them, the rigid motion and ObstacleData's keywords from the caller."""
+        return ObstacleData(self.slots, self.chi, self.udef_corrected, self.cm, vel, omega, **kw)
+
+    def surface(self, vel, omega):
+        """The ObstacleSurface of this obstacle for ComputeForces: the blocks that have surface points, with their corrected udef."""
+        keep = np.where(np.diff(self.first) > 0)[0]
+        first = np.concatenate([[0], np.cumsum(np.diff(self.first)[keep])]).astype(np.int32)
+        return ObstacleSurface(self.slots[keep], first, self.ijk, self.dchi, self.udef_corrected[keep], self.cm, vel, omega)
+
+
+class CreateObstacles(Operator):
+    """CreateObstacles::operator()(dt), main.cpp:13589-13621, from 13596 to 13619 for sim.shapes (ObstacleShape list), after the host
+    has run updateUinf / update / create: the resident chi cleared, KernelCharacteristicFunction, kernelComputeGridCoM and the three
+    kernel*UdefMomenta (cup3d_create_obstacles).  Fills each ObstacleShape (see there).  Where sim.obstacles lists one ObstacleData per
+    shape, their slots, chi, udef and cm are replaced by the new ones -- the rigid motion stays -- and where it is empty it is filled
+    with shape.data(0, 0), so that the operators after this one see the new obstacle.  A collective where the grid is spread over ranks."""
+
+    def __call__(self, dt=0):
+        s = self.sim
+        shapes = getattr(s, "shapes", None)
+        if not shapes:
+            return
+        arr = (capi.ObstacleShape * len(shapes))()
+        out = []
+        for o, a in zip(shapes, arr):
+            n = len(o.slots)
+            w = dict(udef=o.udef.copy(), chi=np.zeros((n, 8, 8, 8)), block_com=np.zeros((n, 4)), block_momenta=np.zeros((n, 13)),
+                     first=np.zeros(n + 1, dtype=np.int32), ijk=np.zeros((512 * n, 3), dtype=np.int32), dchi=np.zeros((512 * n, 3)), delta=np.zeros(512 * n))
+            a.nblocks = n
+            a.slots, a.sdf = o.slots.ctypes.data, o.sdf.ctypes.data
+            for k, v in w.items():
+                setattr(a, k, v.ctypes.data)
+            for d in range(3):
+                a.transvel_correction[d] = o.transvel_correction[d]
+            out.append(w)
+        check(lib().cup3d_create_obstacles(s.handle, len(shapes), arr))
+        for o, a, w in zip(shapes, arr, out):
+            npts = int(w["first"][-1])
+            o.chi, o.udef_corrected, o.block_com, o.block_momenta, o.first = w["chi"], w["udef"], w["block_com"], w["block_momenta"], w["first"]
+            o.ijk, o.dchi, o.delta = w["ijk"][:npts].copy(), w["dchi"][:npts].copy(), w["delta"][:npts].copy()
+            o.transvel_correction, o.angvel_correction = np.array(a.transvel_correction[:]), np.array(a.angvel_correction[:])
+            o.cm, o.mass, o.J = np.array(a.cm[:]), float(a.mass), np.array(a.J[:])
+            o.com_totals, o.udef_totals = np.array(a.com_totals[:]), np.array(a.udef_totals[:])
+        if not s.obstacles:
+            s.obstacles = [o.data((0, 0, 0), (0, 0, 0)) for o in shapes]
+        elif len(s.obstacles) == len(shapes):
+            for d, o in zip(s.obstacles, shapes):
+                d.slots, d.chi, d.udef, d.cm = o.slots, o.chi, o.udef_corrected, o.cm.copy()
+        s.chi_resident = True
+
+
 class UpdateObstacles(Operator):
     """UpdateObstacles::operator()(dt), main.cpp:13812-13837, for sim.obstacles (ObstacleData list): KernelIntegrateFluidMomenta on the
     resident vel, then kernelFinalizeObstacleVel and Obstacle::computeVelocities without the collision override (cup3d_update_obstacles).
@@ -710,12 +780,16 @@ class Simulation:
 
     def __init__(self, sim, obstacle_operators=False):
         """obstacle_operators: with sim.obstacles, put UpdateObstacles and Penalization between the forcing and PressureProjection
-        (15235-15243) -- the resident obstacle step.  Off by default: the caller then runs Penalization itself."""
+        (15235-15243) -- the resident obstacle step -- and, where sim.shapes is set (ObstacleShape list), CreateObstacles in front of
+        everything.  Off by default: the caller then runs Penalization itself."""
         self.sim, self.obstacle_operators = sim, bool(obstacle_operators)
         self.pipeline = [AdvectionDiffusionImplicit(sim) if sim.implicitDiffusion else AdvectionDiffusion(sim)]  # 15231-15234
         if sim.uMax_forced > 0:
             self.pipeline.append(ExternalForcing(sim))
-        if self.obstacle_operators and sim.obstacles:
+        shapes = getattr(sim, "shapes", None)   # ObstacleShape list: CreateObstacles comes first, as in setupOperators (15230)
+        if self.obstacle_operators and shapes:
+            self.pipeline.insert(0, CreateObstacles(sim))
+        if self.obstacle_operators and (sim.obstacles or shapes):
             self.pipeline += [UpdateObstacles(sim), Penalization(sim)]
         self.pipeline.append(PressureProjection(sim))
 

@@ -333,7 +333,8 @@ CUP3D_API int cup3d_adapt_transfer(cup3d_sim_t *src, cup3d_sim_t *dst, int field
  * new owner; the result equals the one-rank cup3d_adapt_transfer bit for bit, block by block. */
 CUP3D_API int cup3d_adapt_migrate(const cup3d_grid_t *old_mesh, const int32_t *old_owner, cup3d_sim_t *src, const cup3d_grid_t *new_mesh,
                         const int32_t *new_owner, cup3d_sim_t *dst, int field);
-/* Obstacle operators (the obstacles themselves -- geometry, chi/udef rasterisation, rigid-body integration -- stay on the host).
+/* Obstacle operators (the obstacles themselves -- geometry, i.e. the signed distance and the deformation velocity, and the rigid-body
+ * integration -- stay on the host; cup3d_create_obstacles below turns the signed distance into chi, surface points and corrected udef).
  * One cup3d_obstacle = the ObstacleBlocks of one Obstacle on this rank in the reference's own layout (struct ObstacleBlock,
  * main.cpp:7256-7263) plus its rigid motion. */
 typedef struct {
@@ -384,6 +385,52 @@ typedef struct {
 } cup3d_obstacle_motion;
 CUP3D_API int cup3d_update_obstacles(cup3d_sim_t *, double dt, double lambda, int implicit_penalization, int nobstacles,
                                      cup3d_obstacle *obstacles, cup3d_obstacle_motion *motion);
+/* The grid half of CreateObstacles::operator() (main.cpp:13596-13619), the first operator of the obstacle step: what the host's geometry
+ * left in ObstacleBlock::sdfLab and ObstacleBlock::udef becomes everything the operators above take -- the blocks' chi, the resident chi
+ * field, the momentum-corrected udef, the centre of mass and the surface list cup3d_compute_forces reads.  One cup3d_obstacle_shape = the
+ * ObstacleBlocks of one Obstacle on this rank.  In the reference's order, obstacles one after the other:
+ *   the resident chi of every block of the sim is set to 0 (13596-13600);
+ *   KernelCharacteristicFunction::operate (13298-13403) on the device, one wavefront per ObstacleBlock: chi by the |sdf| > h test or the
+ *     band formula, resident chi = std::max(chi, resident), the four sums mass, CoM_x, CoM_y, CoM_z over all 512 cells in z, y, x order,
+ *     and the surface points -- one-sided gradH at index 0 and 7, the < 1e-12 and Delta > EPS tests, dchi = -delta * gradU (7426-7428)
+ *     -- in the reference's push_back order: cells in z, y, x, blocks in the order listed.  Bit for bit what the reference computes;
+ *   kernelComputeGridCoM (13406-13425) on the host: block rows added in ascending slot order, all-reduced;
+ *   _kernelIntegrateUdefMomenta (13426-13488) on the device with that centre of mass and transvel_correction as passed in (oldCorrVel):
+ *     per block V, FX FY FZ, TX TY TZ, J0..J5, cells with chi <= 0 skipped, bit for bit;
+ *   kernelAccumulateUdefMomenta (13495-13550) on the host: rows in ascending slot order, all-reduced, invertSym with its detJ guard;
+ *   kernelRemoveUdefMomenta (13551-13588) on the device, then chi, udef and the surface come back.
+ * DOWNLOADS (cup3d_run_stats.field_bytes_downloaded), per obstacle of nblocks blocks and npoints = first[nblocks] surface points:
+ * nblocks * (4*8 + 4) for the blocks' mass / CoM rows and point counts, nblocks * 13*8 for their momenta, nblocks * 2048*8 for chi and
+ * udef, npoints * (3*4 + 4*8) for ijk, dchi and delta: only the points that exist cross the host boundary.
+ * LEFT TO THE HOST: updateUinf, update() and create() (the geometry: sdfLab and udef), finalize() (empty in Obstacle), the MeshChanged /
+ * StaticObstacles gate (13592-13594), and ObstacleBlock::allocate_surface.
+ * COLLECTIVE like cup3d_update_obstacles: every rank calls it with the same nobstacles; a rank that holds none of an obstacle's blocks
+ * passes nblocks = 0.  Per obstacle the 4 and the 13 totals travel with an error flag in two all-reduces of at most 16 values from a
+ * device buffer of the call's own: a rank whose own arguments are refused still takes part and returns its own code, the others
+ * CUP3D_ECOMM, and every rank returns.
+ * CUP3D_EINVAL: a null handle, nobstacles < 0, null shapes with nobstacles > 0, nblocks < 0, a null slots / sdf / udef / chi / first /
+ * ijk / dchi / delta with nblocks > 0, a slot outside [0, nblocks of the sim) -- all checked before anything is written, on the device or
+ * the host -- and, after the all-reduces and so on every rank alike, com_totals[0] <= DBL_EPSILON or udef_totals[0] <= DBL_EPSILON (the
+ * reference's asserts, 13420 and 13520).  A refused call writes nothing of the caller's, for any obstacle of the call; after one of the
+ * two volume failures, and after CUP3D_ECOMM, the resident chi is UNSPECIFIED (cleared, with some obstacles of the call already entered).
+ * nobstacles = 0 is a no-op that clears nothing (13590). */
+typedef struct {
+  long nblocks;
+  const int32_t *slots;  /* as in cup3d_obstacle; distinct within one obstacle, as its ObstacleBlocks are */
+  const double *sdf;     /* in  [nblocks][10][10][10]  ObstacleBlock::sdfLab, index [z+1][y+1][x+1] */
+  double *udef;          /* in/out [nblocks][8][8][8][3]: kernelRemoveUdefMomenta applied */
+  double *chi;           /* out [nblocks][8][8][8] */
+  double transvel_correction[3];  /* in/out: read as oldCorrVel (13436), written at 13533-13535 */
+  double angvel_correction[3];    /* out 13542-13547 */
+  double cm[3], mass, J[6];       /* out: centerOfMass 13421-13423, mass 13532, J 13536-13541 */
+  double com_totals[4], udef_totals[13];  /* out: com[] after 13419, M[] after 13519 */
+  double *block_com;     /* out, may be NULL [nblocks][4]: mass, CoM_x, CoM_y, CoM_z */
+  double *block_momenta; /* out, may be NULL [nblocks][13]: V FX FY FZ TX TY TZ J0..J5 */
+  int32_t *first;        /* out [nblocks+1] CSR, blocks in the order listed */
+  int32_t *ijk;          /* out [.][3], caller-sized for 512*nblocks points, the first first[nblocks] written */
+  double *dchi, *delta;  /* out, same sizing: surface_data::dchidx,y,z ([.][3]) and delta */
+} cup3d_obstacle_shape;
+CUP3D_API int cup3d_create_obstacles(cup3d_sim_t *, int nobstacles, cup3d_obstacle_shape *shapes);
 /* ComputeForces::operator() without Obstacle::computeForces (main.cpp:12496-12503): KernelComputeForces::visit (12273-12493) on the
  * device.  One cup3d_obstacle_surface = the ObstacleBlocks of one Obstacle on this rank that have surface points (nPoints > 0; 12280
  * skips the others) with their surface_data as a CSR list: block i owns points [first[i], first[i+1]), ijk = surface_data::ix, iy, iz,

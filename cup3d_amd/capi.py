@@ -80,6 +80,13 @@ class ObstacleShape(C.Structure):
                 ("block_momenta", C.c_void_p), ("first", C.c_void_p), ("ijk", C.c_void_p), ("dchi", C.c_void_p), ("delta", C.c_void_p)]
 
 
+class ObstacleCollision(C.Structure):
+    """cup3d_obstacle_collision"""
+    _fields_ = [("cm", C.c_double * 3), ("mass", C.c_double), ("J", C.c_double * 6), ("forced", C.c_int * 3), ("vel", C.c_double * 3),
+                ("omega", C.c_double * 3), ("collision_vel", C.c_double * 3), ("collision_omega", C.c_double * 3), ("collision_counter", C.c_double),
+                ("sums", C.c_double * 20)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/cup3d_hip.h
 SIGNATURES = {
     "cup3d_last_error": (C.c_char_p, []),
@@ -168,6 +175,7 @@ SIGNATURES = {
     "cup3d_update_tmpv": (C.c_int, [_vp, C.c_int, C.POINTER(Obstacle)]),
     "cup3d_update_obstacles": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Obstacle), C.POINTER(ObstacleMotion)]),
     "cup3d_create_obstacles": (C.c_int, [_vp, C.c_int, C.POINTER(ObstacleShape)]),
+    "cup3d_prevent_colliding_obstacles": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleCollision), _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cup3d_compute_forces": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_compute_forces_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_profile_enable": (C.c_int, [C.c_int]),

@@ -533,6 +533,7 @@ void cup3d_sim_destroy(cup3d_sim_t *h) {
   mg_destroy(s);
   labs_destroy(s);
   forces_destroy(s);
+  retained_destroy(s);
   double *ptrs[] = {s->vel, s->vel2, s->tmpV, s->pres, s->lhs, s->chi, s->pold, s->d_partials, s->d_red, s->halo_recv, s->halo_send, s->d_block_dots,
                     s->d_hb, s->d_flux};
   for (double *p : ptrs) if (p) hipFree(p);

@@ -139,6 +139,9 @@ struct Sim {
   struct LabTables *labs = nullptr;  // tables and staging buffer of cup3d_sim_labs (amr.hip), built on first use
   struct LabsView *labs_view = nullptr;  // cup3d_sim_labs_over_ranks: the rank's tensorial view, its tables, the ghost pool (amr.hip)
   struct ForcesScratch *forces = nullptr;  // cup3d_compute_forces: tile scratch and staged surface arrays, grow-only (obstacles.hip)
+  // what the last successful cup3d_create_obstacles left on the device, per obstacle of that call: slots, geom, sdfLab, chi and the
+  // corrected udef -- what cup3d_prevent_colliding_obstacles reads (obstacles.hip); nullptr: nothing retained
+  struct RetainedObstacles *retained = nullptr;
   int max_groups = 0;
   // staging for host transfers
   double *d_stage = nullptr;
@@ -235,6 +238,7 @@ int mg_vcycle(Sim *s, const double *in, double *out);
 void mg_destroy(Sim *s);
 void labs_destroy(Sim *s);  // what cup3d_sim_labs and cup3d_sim_labs_over_ranks built on first use (amr.hip)
 void forces_destroy(Sim *s);  // the scratch of cup3d_compute_forces (obstacles.hip)
+void retained_destroy(Sim *s);  // the obstacle blocks cup3d_create_obstacles keeps (obstacles.hip)
 // implicit diffusion (DiffusionSolver, main.cpp:6719-7147): Helmholtz operator of velocity component `direction`
 struct HelmholtzOp { int direction; double dt, nu; };
 int launch_lhs_diffusion(Sim *s, const double *p, double *out, const HelmholtzOp &op);

@@ -485,8 +485,9 @@ class ObstacleData:
     """Host-side description of one obstacle for the device operators: the non-null ObstacleBlocks (block slots, chi, udef in the
     reference's layout, main.cpp:7256-7263) and the rigid motion (centre of mass, translation and angular velocity)."""
 
-    def __init__(self, slots, chi, udef, cm, vel, omega, *, forced=(0, 0, 0), block_rotation=(0, 0, 0), vel_imposed=(0, 0, 0)):
-        """forced / block_rotation / vel_imposed: Obstacle::bForcedInSimFrame, bBlockRotation and transVel_imposed, read by UpdateObstacles."""
+    def __init__(self, slots, chi, udef, cm, vel, omega, *, forced=(0, 0, 0), block_rotation=(0, 0, 0), vel_imposed=(0, 0, 0), mass=0.0, J=(0, 0, 0, 0, 0, 0)):
+        """forced / block_rotation / vel_imposed: Obstacle::bForcedInSimFrame, bBlockRotation and transVel_imposed, read by UpdateObstacles.
+        mass / J: Obstacle::mass and J as CreateObstacles left them, read by PreventCollidingObstacles."""
         self.slots = np.ascontiguousarray(slots, dtype=np.int32)
         self.chi = np.ascontiguousarray(chi, dtype=np.float64).reshape(len(self.slots), 8, 8, 8)
         self.udef = np.ascontiguousarray(udef, dtype=np.float64).reshape(len(self.slots), 8, 8, 8, 3)
@@ -496,6 +497,10 @@ class ObstacleData:
         self.vel_imposed = np.array(vel_imposed, dtype=np.float64)
         # what UpdateObstacles leaves: transVel_computed / angVel_computed, M (29 totals) and the blocks' 29 sums
         self.vel_computed, self.omega_computed, self.totals, self.block_sums = None, None, None, None
+        self.mass, self.J = float(mass), np.array(J, dtype=np.float64)
+        # u/v/w_collision, ox/oy/oz_collision and collision_counter (7546): written by PreventCollidingObstacles, read by UpdateObstacles;
+        # collision_sums: the obstacle's CollisionInfo (20 values) of the last call
+        self.collision_vel, self.collision_omega, self.collision_counter, self.collision_sums = np.zeros(3), np.zeros(3), 0.0, None
 
 
 def _obstacle_array(obstacles):
@@ -529,6 +534,8 @@ class ObstacleShape:
     def data(self, vel, omega, **kw):
         """The ObstacleData of this obstacle for UpdateObstacles / Penalization / PressureProjection: slots, chi, the corrected udef and
         the centre of mass as CreateObstacles left them, the rigid motion and ObstacleData's keywords from the caller."""
+        kw.setdefault("mass", self.mass)
+        kw.setdefault("J", self.J)
         return ObstacleData(self.slots, self.chi, self.udef_corrected, self.cm, vel, omega, **kw)
 
     def surface(self, vel, omega):
@@ -576,6 +583,7 @@ class CreateObstacles(Operator):
         elif len(s.obstacles) == len(shapes):
             for d, o in zip(s.obstacles, shapes):
                 d.slots, d.chi, d.udef, d.cm = o.slots, o.chi, o.udef_corrected, o.cm.copy()
+                d.mass, d.J = o.mass, o.J.copy()
         s.chi_resident = True
 
 
@@ -602,6 +610,41 @@ class UpdateObstacles(Operator):
             o.vel, o.omega = np.array(a.vel[:]), np.array(a.omega[:])
             o.vel_computed, o.omega_computed = np.array(m.vel_computed[:]), np.array(m.omega_computed[:])
             o.totals, o.block_sums = np.array(m.totals[:]), b
+            if o.collision_counter > 0:   # 13069-13077: the velocities PreventCollidingObstacles stored hold while the counter runs
+                o.collision_counter -= dt
+                o.vel, o.omega = o.collision_vel.copy(), o.collision_omega.copy()
+
+
+class PreventCollidingObstacles(Operator):
+    """Penalization::preventCollidingObstacles (main.cpp:14009-14324), what Penalization::operator() begins with (14329), for sim.obstacles
+    (ObstacleData list, one per shape of the last CreateObstacles, whose blocks the device still holds): the CollisionInfo sums on the
+    device, the all-reduces and the elastic collision of every touching pair on the host (cup3d_prevent_colliding_obstacles).  Replaces
+    vel / omega of the obstacles of a resolved pair, stores them with collision_counter = 0.01 dt for UpdateObstacles, leaves each
+    obstacle's collision_sums and sets sim.bCollision / sim.bCollisionID.  A collective where the grid is spread over ranks."""
+
+    def __call__(self, dt):
+        s = self.sim
+        s.bCollisionID = []   # 14013
+        if not s.obstacles:
+            return
+        n = len(s.obstacles)
+        arr = (capi.ObstacleCollision * n)()
+        for o, a in zip(s.obstacles, arr):
+            a.mass, a.collision_counter = o.mass, o.collision_counter
+            for d in range(3):
+                a.cm[d], a.forced[d], a.vel[d], a.omega[d] = o.cm[d], o.forced[d], o.vel[d], o.omega[d]
+                a.collision_vel[d], a.collision_omega[d] = o.collision_vel[d], o.collision_omega[d]
+            for q in range(6):
+                a.J[q] = o.J[q]
+        ids = np.zeros(max(1, n * (n - 1)), dtype=np.int32)
+        nids, hit = C.c_int(0), C.c_int(0)
+        check(lib().cup3d_prevent_colliding_obstacles(s.handle, dt, n, arr, ids.ctypes.data_as(C.c_void_p), C.byref(nids), C.byref(hit)))
+        for o, a in zip(s.obstacles, arr):
+            o.vel, o.omega = np.array(a.vel[:]), np.array(a.omega[:])
+            o.collision_vel, o.collision_omega, o.collision_counter = np.array(a.collision_vel[:]), np.array(a.collision_omega[:]), float(a.collision_counter)
+            o.collision_sums = np.array(a.sums[:])
+        s.bCollisionID = ids[:nids.value].tolist()
+        s.bCollision = bool(getattr(s, "bCollision", False)) or bool(hit.value)   # 14246: set, never cleared
 
 
 class Penalization(Operator):
@@ -778,11 +821,13 @@ class Simulation:
     """The time loop of struct Simulation restricted to the hot path (no obstacles, frozen mesh):
     calcMaxTimestep 15254-15305, advance 15306-15326, pipeline order of setupOperators 15229-15246."""
 
-    def __init__(self, sim, obstacle_operators=False):
+    def __init__(self, sim, obstacle_operators=False, collisions=False):
         """obstacle_operators: with sim.obstacles, put UpdateObstacles and Penalization between the forcing and PressureProjection
         (15235-15243) -- the resident obstacle step -- and, where sim.shapes is set (ObstacleShape list), CreateObstacles in front of
-        everything.  Off by default: the caller then runs Penalization itself."""
-        self.sim, self.obstacle_operators = sim, bool(obstacle_operators)
+        everything.  Off by default: the caller then runs Penalization itself.
+        collisions: with obstacle_operators, PreventCollidingObstacles directly in front of Penalization (14329); it needs the blocks
+        CreateObstacles leaves on the device, i.e. sim.shapes."""
+        self.sim, self.obstacle_operators, self.collisions = sim, bool(obstacle_operators), bool(collisions)
         self.pipeline = [AdvectionDiffusionImplicit(sim) if sim.implicitDiffusion else AdvectionDiffusion(sim)]  # 15231-15234
         if sim.uMax_forced > 0:
             self.pipeline.append(ExternalForcing(sim))
@@ -790,7 +835,7 @@ class Simulation:
         if self.obstacle_operators and shapes:
             self.pipeline.insert(0, CreateObstacles(sim))
         if self.obstacle_operators and (sim.obstacles or shapes):
-            self.pipeline += [UpdateObstacles(sim), Penalization(sim)]
+            self.pipeline += [UpdateObstacles(sim)] + ([PreventCollidingObstacles(sim)] if self.collisions else []) + [Penalization(sim)]
         self.pipeline.append(PressureProjection(sim))
 
     def adaptMesh(self, Rtol, Ctol):
@@ -803,7 +848,7 @@ class Simulation:
             GradChiOnTmp(s)(0)
         st = s.grid.valid_states(MeshAdaptation(Rtol, Ctol).Tag(s, "tmpV"))
         if (st != 0).any():
-            self.__init__(s.adapted(st), self.obstacle_operators)
+            self.__init__(s.adapted(st), self.obstacle_operators, self.collisions)
         return st
 
     def adaptMeshOverRanks(self, mesh, owner, rank, nranks, Rtol, Ctol, allgather):
@@ -825,7 +870,7 @@ class Simulation:
         if not (st != 0).any():
             return st, mesh, owner
         new, new_mesh, new_owner = s.adapted_over_ranks(mesh, owner, st, rank, nranks)
-        self.__init__(new, self.obstacle_operators)
+        self.__init__(new, self.obstacle_operators, self.collisions)
         return st, new_mesh, new_owner
 
     def calcMaxTimestep(self):

@@ -346,7 +346,8 @@ typedef struct {
   double force[3], torque[3];     /* out of cup3d_penalization: Obstacle::force / torque (13932-13937) */
 } cup3d_obstacle;
 /* Penalization::operator() without the collision model (14330-14340): KernelPenalization (13841-13912) on the resident vel with
- * the resident chi, obstacle after obstacle, then kernelFinalizePenalizationForce (13913-13938) */
+ * the resident chi, obstacle after obstacle, then kernelFinalizePenalizationForce (13913-13938).  The collision model it begins with
+ * (preventCollidingObstacles, 14329) is cup3d_prevent_colliding_obstacles below: call that first where bodies may touch. */
 CUP3D_API int cup3d_penalization(cup3d_sim_t *, double dt, double lambda, int implicit_penalization, int nobstacles, cup3d_obstacle *obstacles);
 /* kernelUpdateTmpV (14948-14979): tmpV += udef where chi <= the obstacle's chi; call after clearing tmpV and before
  * cup3d_pressure_rhs / cup3d_pressure_project (15066-15085) */
@@ -367,7 +368,8 @@ CUP3D_API int cup3d_update_tmpv(cup3d_sim_t *, int nobstacles, const cup3d_obsta
  * On return obstacles[k].vel / omega hold the new transVel / angVel -- forced components equal vel_imposed, blocked rotations are 0,
  * everything else is the computed value (13039-13068) -- and the same array goes straight into cup3d_penalization.  vel is only read.
  * LEFT TO THE HOST: the force / torque of 13030-13038 (Penalization overwrites them), bBreakSymmetry's edit of transVel_imposed
- * (12961-12966: pass the edited value), the collision override (13069 ff.), and the asserts on mass and J (13788-13794).
+ * (12961-12966: pass the edited value), the collision override (13069 ff.: the stored velocities of cup3d_prevent_colliding_obstacles while
+ * collision_counter > 0), and the asserts on mass and J (13788-13794).
  * COLLECTIVE like cup3d_penalization: every rank calls it with the same nobstacles; a rank that holds none of an obstacle's blocks passes
  * nblocks = 0.  Per obstacle the 29 totals and an error flag cross the ranks as two all-reduces of at most 16 values from a device buffer
  * of the call's own: a rank whose own arguments fail returns its own code, the others CUP3D_ECOMM, and every rank returns.
@@ -431,6 +433,38 @@ typedef struct {
   double *dchi, *delta;  /* out, same sizing: surface_data::dchidx,y,z ([.][3]) and delta */
 } cup3d_obstacle_shape;
 CUP3D_API int cup3d_create_obstacles(cup3d_sim_t *, int nobstacles, cup3d_obstacle_shape *shapes);
+/* Penalization::preventCollidingObstacles (main.cpp:14009-14324), the collision model Penalization::operator() begins with (14329): call
+ * it between cup3d_update_obstacles and cup3d_penalization.  It reads what the last successful cup3d_create_obstacles of this sim KEEPS
+ * on the device per obstacle of that call -- slots, geom [n][4], sdfLab [n][10][10][10], chi [n][8][8][8] and the corrected udef
+ * [n][8][8][8][3], counted in cup3d_sim_device_bytes, replaced by the next successful call, dropped by a refused or failed one, freed by
+ * cup3d_sim_destroy -- so no field is uploaded and 20 doubles per obstacle come back (cup3d_run_stats.field_bytes_downloaded).
+ *   The CollisionInfo sums (14037-14142) on the device, one wavefront per obstacle i: for j = 0..N-1, j != i, the blocks both obstacles
+ *     hold in ascending slot order whatever order the lists have, cells in z, y, x order, those with iChi <= 0 or jChi <= 0 skipped; iM,
+ *     iPos, ivec, jM, jPos, jvec run on across the blocks and across j; iMom / jMom are those of the first cell whose |Mom|^2 beats
+ *     imagmax / jmagmax with the strict `>`, the two maxima restart at 0 for every j and iMom / jMom persist when no cell beats 0, as
+ *     written.  Bit for bit the reference's loop with one thread.
+ *   On the host: buffermax and the MPI_MAX all-reduce (14143-14153), the iok / jok test with its 1e-10 (14154-14182), the MPI_SUM of
+ *     20 N (14183), then the pairs i < j in order with one thread (14208-14323) -- the tolerance and 0.2 tests, the push onto
+ *     bCollisionID, the normal, projVel <= 0, the contact point, the 1e10 mass of a forced body, ComputeJ and ElasticCollision as written
+ *     (13939-14007, the 1e-21 terms included) -- and later pairs see the velocities earlier pairs wrote.
+ * COLLECTIVE like cup3d_update_obstacles: every rank calls it with the same nobstacles.  Both all-reduces go in pieces of at most 16
+ * values from a device buffer of the call's own; an error flag rides with the first piece: a rank whose own arguments fail returns its
+ * own code, the others CUP3D_ECOMM, and every rank returns.
+ * CUP3D_EINVAL: a null handle, dt <= 0, nobstacles < 0, null obstacles / ncollided / any with nobstacles > 0.  CUP3D_ESTATE: nothing
+ * retained, or nobstacles differs from the retained count.  A refused call writes nothing of the caller's.  nobstacles = 0 is a no-op
+ * and nobstacles = 1 finds nothing.  LEFT TO THE HOST: the override of 13069-13077 while collision_counter > 0 (UpdateObstacles). */
+typedef struct {
+  double cm[3], mass, J[6];      /* centerOfMass, mass, J as cup3d_create_obstacles returned them */
+  int forced[3];                 /* bForcedInSimFrame */
+  double vel[3], omega[3];       /* in/out: transVel, angVel */
+  double collision_vel[3], collision_omega[3], collision_counter; /* in/out: u/v/w_collision, ox/oy/oz_collision, collision_counter;
+                                    written only for an obstacle of a resolved pair (14309-14322) */
+  double sums[20];               /* out: CollisionInfo after both all-reduces, member order of 14015-14034 */
+} cup3d_obstacle_collision;
+/* collided: may be NULL, room for nobstacles*(nobstacles-1) ints; *ncollided ints written = sim.bCollisionID (pushed at 14249-14250,
+ * i.e. BEFORE the projVel test, as written); *any = whether sim.bCollision was set */
+CUP3D_API int cup3d_prevent_colliding_obstacles(cup3d_sim_t *, double dt, int nobstacles, cup3d_obstacle_collision *obstacles,
+                                                int32_t *collided, int *ncollided, int *any);
 /* ComputeForces::operator() without Obstacle::computeForces (main.cpp:12496-12503): KernelComputeForces::visit (12273-12493) on the
  * device.  One cup3d_obstacle_surface = the ObstacleBlocks of one Obstacle on this rank that have surface points (nPoints > 0; 12280
  * skips the others) with their surface_data as a CSR list: block i owns points [first[i], first[i+1]), ijk = surface_data::ix, iy, iz,

@@ -66,6 +66,11 @@ class ObstacleMotion(C.Structure):
                 ("totals", C.c_double * 29), ("vel_computed", C.c_double * 3), ("omega_computed", C.c_double * 3)]
 
 
+class ObstacleBody(C.Structure):
+    """cup3d_obstacle_body"""
+    _fields_ = [("cm", C.c_double * 3), ("vel", C.c_double * 3), ("omega", C.c_double * 3), ("force", C.c_double * 3), ("torque", C.c_double * 3)]
+
+
 class ObstacleSurface(C.Structure):
     """cup3d_obstacle_surface"""
     _fields_ = [("nblocks", C.c_long), ("slots", C.c_void_p), ("first", C.c_void_p), ("ijk", C.c_void_p), ("dchi", C.c_void_p), ("udef", C.c_void_p),
@@ -176,6 +181,9 @@ SIGNATURES = {
     "cup3d_update_obstacles": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Obstacle), C.POINTER(ObstacleMotion)]),
     "cup3d_create_obstacles": (C.c_int, [_vp, C.c_int, C.POINTER(ObstacleShape)]),
     "cup3d_prevent_colliding_obstacles": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleCollision), _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cup3d_update_obstacles_resident": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(ObstacleBody), C.POINTER(ObstacleMotion)]),
+    "cup3d_penalization_resident": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(ObstacleBody)]),
+    "cup3d_update_tmpv_resident": (C.c_int, [_vp, C.c_int]),
     "cup3d_compute_forces": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_compute_forces_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_profile_enable": (C.c_int, [C.c_int]),

@@ -4,7 +4,8 @@
 // The obstacles themselves (geometry -- the signed distance and the deformation velocity -- and rigid-body integration) stay on the host;
 // cup3d_create_obstacles turns the signed distance into chi, surface points and momentum-free udef, and the other kernels take the
 // ObstacleBlocks of one obstacle at a time -- chi[8][8][8] and udef[8][8][8][3] in the reference's own (AoS) layout -- so the
-// velocity does not have to leave HBM between AdvectionDiffusion and PressureProjection when obstacles are present.
+// velocity does not have to leave HBM between AdvectionDiffusion and PressureProjection when obstacles are present.  The *_resident
+// entry points run UpdateObstacles, Penalization and kernelUpdateTmpV on the blocks cup3d_create_obstacles keeps, all obstacles at once.
 // Velocities and tmpV are bit-exact with the reference; the penalisation force / torque sums are reductions (block totals summed in block
 // order on the host, cells within a block in tree order on the device); the momenta of UpdateObstacles and the surface sums of
 // ComputeForces are added in the reference's own order and are bit-exact per block.
@@ -26,11 +27,12 @@ struct ObstItems {
   const double *udef;    // [n][512][3]
 };
 
-__global__ void __launch_bounds__(256) k_penalize(ObstItems it, double *__restrict__ vel, const double *__restrict__ chi_field, double dt,
-                                                   double lambdaFac, int implicit, double cm0, double cm1, double cm2, double v0, double v1, double v2,
-                                                   double o0, double o1, double o2, double *__restrict__ forces /* [n][6] */) {
-  __shared__ double red[4];
-  const int i = blockIdx.x, t = threadIdx.x;
+// KernelPenalization on ObstacleBlock i of `it` by one 256-thread workgroup; the block's six sums go to forces[0..5].  The body of both
+// k_penalize and k_penalize_set: a thread owns cells t and 256 + t of the slot.
+__device__ __forceinline__ void penalize_block(const ObstItems &it, const int i, double *__restrict__ vel, const double *__restrict__ chi_field, double dt,
+                                               double lambdaFac, int implicit, double cm0, double cm1, double cm2, double v0, double v1, double v2,
+                                               double o0, double o1, double o2, double *__restrict__ forces /* [6] */, double *red /* LDS [4] */) {
+  const int t = threadIdx.x;
   const int slot = it.slots[i];
   const double h = it.geom[4 * i], dv = pow(h, 3.0);
   double F[6] = {0, 0, 0, 0, 0, 0};
@@ -60,12 +62,21 @@ __global__ void __launch_bounds__(256) k_penalize(ObstItems it, double *__restri
 #pragma unroll
   for (int q = 0; q < 6; ++q) {
     const double s = group_sum<4>(F[q], red);
-    if (t == 0) forces[(size_t)i * 6 + q] = s;
+    if (t == 0) forces[q] = s;
   }
 }
 
-__global__ void __launch_bounds__(256) k_update_tmpv(ObstItems it, double *__restrict__ tmpV, const double *__restrict__ chi_field) {
-  const int i = blockIdx.x, t = threadIdx.x;
+__global__ void __launch_bounds__(256) k_penalize(ObstItems it, double *__restrict__ vel, const double *__restrict__ chi_field, double dt,
+                                                   double lambdaFac, int implicit, double cm0, double cm1, double cm2, double v0, double v1, double v2,
+                                                   double o0, double o1, double o2, double *__restrict__ forces /* [n][6] */) {
+  __shared__ double red[4];
+  const int i = blockIdx.x;
+  penalize_block(it, i, vel, chi_field, dt, lambdaFac, implicit, cm0, cm1, cm2, v0, v1, v2, o0, o1, o2, forces + (size_t)i * 6, red);
+}
+
+// kernelUpdateTmpV on ObstacleBlock i of `it`; the body of both k_update_tmpv and k_update_tmpv_set
+__device__ __forceinline__ void update_tmpv_block(const ObstItems &it, const int i, double *__restrict__ tmpV, const double *__restrict__ chi_field) {
+  const int t = threadIdx.x;
   const int slot = it.slots[i];
   for (int k = 0; k < 2; ++k) {
     const int c = k * 256 + t;
@@ -74,6 +85,10 @@ __global__ void __launch_bounds__(256) k_update_tmpv(ObstItems it, double *__res
     double *b = tmpV + (size_t)slot * 1536 + c;
     b[0] += U[0]; b[512] += U[1]; b[1024] += U[2];
   }
+}
+
+__global__ void __launch_bounds__(256) k_update_tmpv(ObstItems it, double *__restrict__ tmpV, const double *__restrict__ chi_field) {
+  update_tmpv_block(it, blockIdx.x, tmpV, chi_field);
 }
 
 namespace {
@@ -114,6 +129,44 @@ int stage(const Sim *s, const cup3d_obstacle &o, DevBuf &slots, DevBuf &geom, De
   it->udef = (const double *)udef.p;
   return CUP3D_OK;
 }
+
+// the first `width` columns of rows [n][stride] added in ascending slot order onto total[width]: the reference's loops over
+// obstacleBlocks with one thread
+void add_rows_in_slot_order(const int32_t *slots, long n, const double *rows, int stride, int width, double *total) {
+  std::vector<long> order(n);
+  for (long i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return slots[a] < slots[b]; });
+  for (long i : order)
+    for (int q = 0; q < width; ++q) total[q] += rows[(size_t)i * stride + q];
+}
+
+// The host half of kernelFinalizePenalizationForce (13913-13938) that cup3d_penalization and cup3d_penalization_resident share: obstacle
+// k's six sums M[0..5] cross the ranks, MPI_Allreduce(M, 6) at 13931, on the stream every RCCL call of the library uses.
+// M[6] rides along: 0, or 1 from a rank whose local part failed (rc != 0) -- the ranks agree on the outcome in the collective they hold
+// anyway, so that one rank's bad obstacle returns an error everywhere instead of leaving the others inside the all-reduce
+int penalization_force_over_ranks(Sim *s, const char *who, int k, int rc, double *M /* [7] */) {
+  if (scalars_cross_ranks(s)) {
+    M[6] = rc ? 1.0 : 0.0;
+    double *d = s->d_red;
+    hipStream_t cs = scalar_stream(s);
+    int rc2;
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    CUP3D_HIP(hipMemcpyAsync(d, M, 7 * sizeof(double), hipMemcpyHostToDevice, cs));
+    if ((rc2 = allreduce(s, d, 7, false, cs))) return rc ? rc : rc2;
+    CUP3D_HIP(hipMemcpyAsync(M, d, 7 * sizeof(double), hipMemcpyDeviceToHost, cs));
+    CUP3D_HIP(hipStreamSynchronize(cs));
+    if (!rc && M[6] != 0.0) {
+      set_error("%s: obstacle %d failed on %d other rank(s)", who, k, (int)M[6]);
+      rc = CUP3D_ECOMM;
+    }
+  }
+  return rc;
+}
+
+// Obstacle::force / torque (13932-13937)
+void force_from_sums(const double *M, double *force, double *torque) {
+  for (int d = 0; d < 3; ++d) { force[d] = M[d]; torque[d] = M[3 + d]; }
+}
 }  // namespace
 
 }  // namespace cup3d
@@ -129,9 +182,7 @@ extern "C" int cup3d_penalization(cup3d_sim_t *h, double dt, double lambda, int 
     for (int d = 0; d < 3; ++d) o.force[d] = o.torque[d] = 0.0;
     // A rank whose share of the grid this obstacle does not touch still takes part in the all-reduce below with M = 0: the
     // reference issues MPI_Allreduce(M, 6) for every obstacle on every rank (13931), and skipping it here would pair this rank's
-    // NEXT collective with the other ranks' 6-double sum.
-    // M[6] rides along: 0, or 1 from a rank whose local part failed -- the ranks agree on the outcome in the collective they hold
-    // anyway, so that one rank's bad obstacle returns an error everywhere instead of leaving the others inside the all-reduce
+    // NEXT collective with the other ranks' 6-double sum.  M[6] is penalization_force_over_ranks' flag.
     double M[7] = {0, 0, 0, 0, 0, 0, 0};
     auto local_part = [&]() -> int {
       if (o.nblocks <= 0) return CUP3D_OK;
@@ -151,31 +202,12 @@ extern "C" int cup3d_penalization(cup3d_sim_t *h, double dt, double lambda, int 
       CUP3D_HIP(hipMemcpyAsync(F.data(), forces.p, F.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
       CUP3D_HIP(hipStreamSynchronize(stream()));
       // kernelFinalizePenalizationForce (13913-13938): block totals in block (slot) order
-      std::vector<long> order(o.nblocks);
-      for (long i = 0; i < o.nblocks; ++i) order[i] = i;
-      std::sort(order.begin(), order.end(), [&](long a, long b) { return o.slots[a] < o.slots[b]; });
-      for (long i : order)
-        for (int q = 0; q < 6; ++q) M[q] += F[(size_t)i * 6 + q];
+      add_rows_in_slot_order(o.slots, o.nblocks, F.data(), 6, 6, M);
       return CUP3D_OK;
     };
-    int rc = local_part();
-    if (scalars_cross_ranks(s)) {  // MPI_Allreduce(M, 6), 13931; on the stream every RCCL call of the library uses
-      M[6] = rc ? 1.0 : 0.0;
-      double *d = s->d_red;
-      hipStream_t cs = scalar_stream(s);
-      int rc2;
-      CUP3D_HIP(hipStreamSynchronize(stream()));
-      CUP3D_HIP(hipMemcpyAsync(d, M, 7 * sizeof(double), hipMemcpyHostToDevice, cs));
-      if ((rc2 = allreduce(s, d, 7, false, cs))) return rc ? rc : rc2;
-      CUP3D_HIP(hipMemcpyAsync(M, d, 7 * sizeof(double), hipMemcpyDeviceToHost, cs));
-      CUP3D_HIP(hipStreamSynchronize(cs));
-      if (!rc && M[6] != 0.0) {
-        set_error("cup3d_penalization: obstacle %d failed on %d other rank(s)", k, (int)M[6]);
-        rc = CUP3D_ECOMM;
-      }
-    }
+    int rc = penalization_force_over_ranks(s, "cup3d_penalization", k, local_part(), M);
     if (rc) return rc;
-    for (int d = 0; d < 3; ++d) { o.force[d] = M[d]; o.torque[d] = M[3 + d]; }
+    force_from_sums(M, o.force, o.torque);
   }
   return CUP3D_OK;
 }
@@ -215,10 +247,11 @@ constexpr int kMomentaExplicit = 13;  // penalisation GfX, GpX GpY GpZ, Gj0..Gj5
 // J3..J5 and Gj3..Gj5 are accumulated with -= (13698-13700, 13720-13722)
 constexpr unsigned kMomentaSubtracted = (1u << 10) | (1u << 11) | (1u << 12) | (1u << 20) | (1u << 21) | (1u << 22);
 
-__global__ void __launch_bounds__(64) k_fluid_momenta(ObstItems it, const double *__restrict__ vel, double lambdt, int implicit, double cm0, double cm1,
-                                                       double cm2, double *__restrict__ sums /* [n][29] */) {
-  __shared__ double sm[kMomenta][65];
-  const int b = blockIdx.x, lane = threadIdx.x;
+// KernelIntegrateFluidMomenta on ObstacleBlock b of `it` by one wavefront; the block's 29 sums go to sums[0..28].  The body of both
+// k_fluid_momenta and k_fluid_momenta_set.
+__device__ __forceinline__ void fluid_momenta_block(const ObstItems &it, const int b, const double *__restrict__ vel, double lambdt, int implicit, double cm0,
+                                                    double cm1, double cm2, double *__restrict__ sums /* [29] */, double (*sm)[65] /* LDS [29][65] */) {
+  const int lane = threadIdx.x;
   const int slot = it.slots[b];
   const double h = it.geom[4 * b], dv = h * h * h;  // dvol, 13629
   const int nq = implicit ? kMomenta : kMomentaExplicit;
@@ -281,7 +314,14 @@ __global__ void __launch_bounds__(64) k_fluid_momenta(ObstItems it, const double
     }
     __syncthreads();
   }
-  if (lane < kMomenta) sums[(size_t)b * kMomenta + lane] = lane < nq ? total : 0.0;
+  if (lane < kMomenta) sums[lane] = lane < nq ? total : 0.0;
+}
+
+__global__ void __launch_bounds__(64) k_fluid_momenta(ObstItems it, const double *__restrict__ vel, double lambdt, int implicit, double cm0, double cm1,
+                                                       double cm2, double *__restrict__ sums /* [n][29] */) {
+  __shared__ double sm[kMomenta][65];
+  const int b = blockIdx.x;
+  fluid_momenta_block(it, b, vel, lambdt, implicit, cm0, cm1, cm2, sums + (size_t)b * kMomenta, sm);
 }
 
 namespace {
@@ -348,6 +388,62 @@ void rigid_motion_from_momenta(const double *M, int implicit, const cup3d_obstac
   }
   lu_solve6(A, b, x);
 }
+
+// What cup3d_update_obstacles and cup3d_update_obstacles_resident keep of one obstacle until every obstacle of the call has passed
+struct MomentaResult {
+  const double *rows = nullptr;  // [nblocks][29] in the order listed, or nullptr
+  long nblocks = 0;
+  double M[kMomenta];
+  double x[6];
+};
+
+// The host half of UpdateObstacles for obstacle k once this rank's block rows are added into R.M (rc: what that local part returned):
+// the all-reduce over ranks (13783), the assert on the volume (13795) and Obstacle::computeVelocities.  red: the call's device buffer
+// of 32 doubles where scalars cross ranks.
+int obstacle_motion_from_sums(Sim *s, const char *who, int k, int rc, double *red, int implicit, const cup3d_obstacle_motion &mo, MomentaResult &R) {
+  double *M = R.M;
+  if (scalars_cross_ranks(s)) {
+    // the in-process communicator of the tests carries 16 values per all-reduce: two of them, the second with the flag -- 0, or 1 from a
+    // rank whose local part failed, so that one rank's bad obstacle returns an error everywhere (as in cup3d_penalization)
+    double buf[32] = {0};
+    for (int q = 0; q < kMomenta; ++q) buf[q] = rc ? 0.0 : M[q];
+    buf[kMomenta] = rc ? 1.0 : 0.0;
+    double *d = red;
+    hipStream_t cs = scalar_stream(s);
+    int rc2;
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    CUP3D_HIP(hipMemcpyAsync(d, buf, 32 * sizeof(double), hipMemcpyHostToDevice, cs));
+    if ((rc2 = allreduce(s, d, 16, false, cs)) || (rc2 = allreduce(s, d + 16, kMomenta + 1 - 16, false, cs))) return rc ? rc : rc2;
+    CUP3D_HIP(hipMemcpyAsync(buf, d, 32 * sizeof(double), hipMemcpyDeviceToHost, cs));
+    CUP3D_HIP(hipStreamSynchronize(cs));
+    for (int q = 0; q < kMomenta; ++q) M[q] = buf[q];
+    if (!rc && buf[kMomenta] != 0.0) {
+      set_error("%s: obstacle %d failed on %d other rank(s)", who, k, (int)buf[kMomenta]);
+      rc = CUP3D_ECOMM;
+    }
+  }
+  if (rc) return rc;
+  if (!(M[0] > DBL_EPSILON)) {  // assert(M[0] > EPS), 13795: the same total on every rank
+    set_error("%s: obstacle %d has volume %g", who, k, M[0]);
+    return CUP3D_EINVAL;
+  }
+  rigid_motion_from_momenta(M, implicit, mo, R.x);
+  return CUP3D_OK;
+}
+
+// every obstacle of the call has passed: the caller's arrays of one of them; vel / omega are the obstacle's transVel / angVel
+void write_obstacle_motion(const MomentaResult &R, int nq, cup3d_obstacle_motion &mo, double *vel, double *omega) {
+  if (mo.block_sums)
+    for (long i = 0; i < R.nblocks; ++i)
+      for (int q = 0; q < nq; ++q) mo.block_sums[(size_t)i * kMomenta + q] = R.rows[(size_t)i * kMomenta + q];
+  for (int q = 0; q < kMomenta; ++q) mo.totals[q] = R.M[q];
+  for (int d = 0; d < 3; ++d) {
+    mo.vel_computed[d] = R.x[d];
+    mo.omega_computed[d] = R.x[3 + d];
+    vel[d] = mo.forced[d] ? mo.vel_imposed[d] : R.x[d];      // 13039-13053
+    omega[d] = mo.block_rotation[d] ? 0.0 : R.x[3 + d];      // 13054-13068
+  }
+}
 }  // namespace
 
 }  // namespace cup3d
@@ -358,8 +454,8 @@ extern "C" int cup3d_update_obstacles(cup3d_sim_t *h, double dt, double lambda, 
   const int nq = implicit ? kMomenta : kMomentaExplicit;
   const double lambdt = lambda * dt;  // 13664
   // nothing of the caller's is written before every obstacle of the call has passed: the results wait here
-  struct Result { std::vector<double> rows; double M[kMomenta]; double x[6]; };
-  std::vector<Result> res((size_t)nobst);
+  std::vector<MomentaResult> res((size_t)nobst);
+  std::vector<std::vector<double>> rows((size_t)nobst);
   const bool cross = scalars_cross_ranks(s);
   DevBuf red;  // the all-reduce operand of this call: M[0..15] | M[16..28], error flag
   if (cross && nobst > 0) {
@@ -368,7 +464,7 @@ extern "C" int cup3d_update_obstacles(cup3d_sim_t *h, double dt, double lambda, 
   }
   for (int k = 0; k < nobst; ++k) {  // obstacles one after the other, as kernelFinalizeObstacleVel visits them (13739)
     const cup3d_obstacle &o = obst[k];
-    Result &R = res[k];
+    MomentaResult &R = res[k];
     double *M = R.M;
     for (int q = 0; q < kMomenta; ++q) M[q] = 0.0;
     // a rank that holds none of the obstacle's blocks still takes part in the all-reduce with M = 0 (MPI_Allreduce(M, 29), 13783)
@@ -387,60 +483,20 @@ extern "C" int cup3d_update_obstacles(cup3d_sim_t *h, double dt, double lambda, 
                            o.cm[2], (double *)sums.p);
       }
       CUP3D_HIP(hipGetLastError());
-      R.rows.resize((size_t)o.nblocks * kMomenta);
-      CUP3D_HIP(hipMemcpyAsync(R.rows.data(), sums.p, R.rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      rows[k].resize((size_t)o.nblocks * kMomenta);
+      CUP3D_HIP(hipMemcpyAsync(rows[k].data(), sums.p, rows[k].size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
       CUP3D_HIP(hipStreamSynchronize(stream()));
-      stats_field_download(R.rows.size() * sizeof(double));
+      stats_field_download(rows[k].size() * sizeof(double));
+      R.rows = rows[k].data();
+      R.nblocks = o.nblocks;
       // kernelFinalizeObstacleVel's loop with one thread (13744-13781): block rows in block (slot) order
-      std::vector<long> order(o.nblocks);
-      for (long i = 0; i < o.nblocks; ++i) order[i] = i;
-      std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return o.slots[a] < o.slots[b]; });
-      for (long i : order)
-        for (int q = 0; q < nq; ++q) M[q] += R.rows[(size_t)i * kMomenta + q];
+      add_rows_in_slot_order(o.slots, o.nblocks, R.rows, kMomenta, nq, M);
       return CUP3D_OK;
     };
-    int rc = local_part();
-    if (cross) {
-      // the in-process communicator of the tests carries 16 values per all-reduce: two of them, the second with the flag -- 0, or 1 from a
-      // rank whose local part failed, so that one rank's bad obstacle returns an error everywhere (as in cup3d_penalization)
-      double buf[32] = {0};
-      for (int q = 0; q < kMomenta; ++q) buf[q] = rc ? 0.0 : M[q];
-      buf[kMomenta] = rc ? 1.0 : 0.0;
-      double *d = (double *)red.p;
-      hipStream_t cs = scalar_stream(s);
-      int rc2;
-      CUP3D_HIP(hipStreamSynchronize(stream()));
-      CUP3D_HIP(hipMemcpyAsync(d, buf, 32 * sizeof(double), hipMemcpyHostToDevice, cs));
-      if ((rc2 = allreduce(s, d, 16, false, cs)) || (rc2 = allreduce(s, d + 16, kMomenta + 1 - 16, false, cs))) return rc ? rc : rc2;
-      CUP3D_HIP(hipMemcpyAsync(buf, d, 32 * sizeof(double), hipMemcpyDeviceToHost, cs));
-      CUP3D_HIP(hipStreamSynchronize(cs));
-      for (int q = 0; q < kMomenta; ++q) M[q] = buf[q];
-      if (!rc && buf[kMomenta] != 0.0) {
-        set_error("cup3d_update_obstacles: obstacle %d failed on %d other rank(s)", k, (int)buf[kMomenta]);
-        rc = CUP3D_ECOMM;
-      }
-    }
+    int rc = obstacle_motion_from_sums(s, "cup3d_update_obstacles", k, local_part(), (double *)red.p, implicit, motion[k], R);
     if (rc) return rc;
-    if (!(M[0] > DBL_EPSILON)) {  // assert(M[0] > EPS), 13795: the same total on every rank
-      set_error("cup3d_update_obstacles: obstacle %d has volume %g", k, M[0]);
-      return CUP3D_EINVAL;
-    }
-    rigid_motion_from_momenta(M, implicit, motion[k], R.x);
   }
-  for (int k = 0; k < nobst; ++k) {
-    cup3d_obstacle_motion &mo = motion[k];
-    const Result &R = res[k];
-    if (mo.block_sums)
-      for (long i = 0; i < obst[k].nblocks; ++i)
-        for (int q = 0; q < nq; ++q) mo.block_sums[(size_t)i * kMomenta + q] = R.rows[(size_t)i * kMomenta + q];
-    for (int q = 0; q < kMomenta; ++q) mo.totals[q] = R.M[q];
-    for (int d = 0; d < 3; ++d) {
-      mo.vel_computed[d] = R.x[d];
-      mo.omega_computed[d] = R.x[3 + d];
-      obst[k].vel[d] = mo.forced[d] ? mo.vel_imposed[d] : R.x[d];      // 13039-13053
-      obst[k].omega[d] = mo.block_rotation[d] ? 0.0 : R.x[3 + d];      // 13054-13068
-    }
-  }
+  for (int k = 0; k < nobst; ++k) write_obstacle_motion(res[k], nq, motion[k], obst[k].vel, obst[k].omega);
   return CUP3D_OK;
 }
 
@@ -1076,25 +1132,36 @@ struct ShapeWork {
   double com_totals[4], M[kUdefMomenta], cm[3], transvel[3], angvel[3];
 };
 
-// rows [n][width] added in ascending slot order onto total[width]: the reference's loops over obstacleBlocks with one thread
-void add_rows_in_slot_order(const int32_t *slots, long n, const std::vector<double> &rows, int width, double *total) {
-  std::vector<long> order(n);
-  for (long i = 0; i < n; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return slots[a] < slots[b]; });
-  for (long i : order)
-    for (int q = 0; q < width; ++q) total[q] += rows[(size_t)i * width + q];
-}
 }  // namespace
 
-// The ShapeWork buffers of the last successful cup3d_create_obstacles that the collision model reads, moved here instead of freed.
+// How the resident operators (cup3d_update_obstacles_resident, cup3d_penalization_resident, cup3d_update_tmpv_resident) walk the
+// retained set; built from the slots_h lists by the first of them to run after a cup3d_create_obstacles.
+// Row r = row_base[k] + i stands for block i of obstacle k in the order listed.  The slot-major schedule lists, per distinct slot any
+// obstacle holds, in ascending slot order, the rows of that slot in ascending k (an obstacle's slots are distinct: at most one row per
+// obstacle): rows sched_rows[sched_first[j] .. sched_first[j + 1]) for the j-th slot.
+struct ResidentPlan {
+  long rows = 0, nslots = 0;
+  std::vector<long> row_base;   // [N + 1]
+  DevBuf obst;                  // ObstItems [N]: the retained slots, geom, chi, udef of every obstacle
+  DevBuf row_obst, row_block;   // int32 [rows]: k and i of a row
+  DevBuf sched_first, sched_rows;  // int32 [nslots + 1], [rows]
+  DevBuf body;                  // double [N][9]: the call's cm, vel, omega of every obstacle
+  DevBuf out;                   // double [rows][29]: the call's block rows ([rows][6] for the penalisation forces)
+  size_t bytes = 0;
+};
+
+// The ShapeWork buffers of the last successful cup3d_create_obstacles that the collision model and the resident operators read, moved
+// here instead of freed.
 struct RetainedObstacles {
   struct One {
     long nblocks = 0;
-    std::vector<int32_t> slots_h;       // the caller's slot list, for the intersections
+    std::vector<int32_t> slots_h;       // the caller's slot list, for the intersections and the plan
     DevBuf slots, geom, sdf, chi, udef;  // [n], [n][4], [n][10][10][10], [n][8][8][8], [n][8][8][8][3] (corrected)
   };
   std::vector<One> obst;
-  size_t bytes = 0;  // counted in Sim::bytes
+  ResidentPlan *plan = nullptr;  // nullptr until a resident operator asks for it
+  size_t bytes = 0;  // counted in Sim::bytes, the plan's included once it exists
+  ~RetainedObstacles() { delete plan; }
 };
 
 void retained_destroy(Sim *s) {
@@ -1200,7 +1267,7 @@ static int create_obstacles(Sim *s, int nobst, cup3d_obstacle_shape *shapes, std
                            (double *)W.delta.p);
       }
       CUP3D_HIP(hipGetLastError());
-      add_rows_in_slot_order(o.slots, n, W.com_rows, 4, W.com_totals);  // kernelComputeGridCoM, 13411-13418
+      add_rows_in_slot_order(o.slots, n, W.com_rows.data(), 4, 4, W.com_totals);  // kernelComputeGridCoM, 13411-13418
       return CUP3D_OK;
     };
     rc = over_ranks(W.com_totals, 4, characteristic(), k);  // MPI_Allreduce(com, 4), 13419
@@ -1227,7 +1294,7 @@ static int create_obstacles(Sim *s, int nobst, cup3d_obstacle_shape *shapes, std
       CUP3D_HIP(hipMemcpyAsync(W.momenta_rows.data(), W.momenta.p, W.momenta_rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
       CUP3D_HIP(hipStreamSynchronize(stream()));
       stats_field_download(W.momenta_rows.size() * sizeof(double));
-      add_rows_in_slot_order(o.slots, n, W.momenta_rows, kUdefMomenta, W.M);  // 13501-13517
+      add_rows_in_slot_order(o.slots, n, W.momenta_rows.data(), kUdefMomenta, kUdefMomenta, W.M);  // 13501-13517
       return CUP3D_OK;
     };
     if ((rc = over_ranks(W.M, kUdefMomenta, momenta(), k))) return rc;  // MPI_Allreduce(M, 13), 13519
@@ -1314,6 +1381,262 @@ extern "C" int cup3d_create_obstacles(cup3d_sim_t *h, int nobst, cup3d_obstacle_
   }
   s->retained = R;
   s->bytes += R->bytes;
+  return CUP3D_OK;
+}
+
+// ==== cup3d_update_obstacles_resident / cup3d_penalization_resident / cup3d_update_tmpv_resident.  UpdateObstacles (13812-13837),
+// KernelPenalization + kernelFinalizePenalizationForce (13841-13938) and kernelUpdateTmpV (14948-14979) on the blocks
+// cup3d_create_obstacles retained: no chi or udef goes up, one launch per operator whatever the number of obstacles.
+// k_fluid_momenta_set: one wavefront per row of the plan; obstacles are independent here (vel is only read).
+// k_penalize_set / k_update_tmpv_set: one workgroup per touched slot walks the slot's rows in ascending obstacle order.  A thread owns the
+// same two cells of the slot throughout, so obstacle k + 1 sees what obstacle k wrote, and no other workgroup touches the slot: the
+// reference's order (obstacles one after the other, 13849-13852 and 15072-15078) without a launch per obstacle.
+// The row, its obstacle and the obstacle's arrays are found through the plan's tables: all of them indexed by blockIdx or by values loaded
+// through it, i.e. wave-uniform.
+namespace cup3d {
+
+struct PlanItems {
+  const ObstItems *obst;                  // [N]
+  const int32_t *row_obst, *row_block;    // [rows]
+  const int32_t *sched_first, *sched_rows;  // [nslots + 1], [rows]
+  const double *body;                     // [N][9]: cm, vel, omega
+};
+
+// The plan's tables are written before the launch and only read by the kernels.  Read through the constant address space, a load at a
+// wave-uniform index is a scalar load whatever the kernel stores in between, and what it returns -- the row, its obstacle, the obstacle's
+// array pointers and rigid state -- stays in scalar registers; as plain global loads next to the stores to vel they would be vector
+// loads, and every address formed from them a pair of vector registers.
+template <class T>
+using Constant = const T __attribute__((address_space(4)));
+template <class T>
+__device__ __forceinline__ Constant<T> *constant(const T *p) {
+  return (Constant<T> *)p;
+}
+static_assert(sizeof(ObstItems) == 4 * sizeof(unsigned long long), "plan_obstacle reads an ObstItems as four 64-bit words");
+__device__ __forceinline__ ObstItems plan_obstacle(const PlanItems &pl, int k) {
+  Constant<unsigned long long> *w = constant(reinterpret_cast<const unsigned long long *>(pl.obst)) + 4 * (size_t)k;
+  return ObstItems{reinterpret_cast<const int32_t *>(w[0]), reinterpret_cast<const double *>(w[1]), reinterpret_cast<const double *>(w[2]),
+                   reinterpret_cast<const double *>(w[3])};
+}
+
+__global__ void __launch_bounds__(64) k_fluid_momenta_set(PlanItems pl, const double *__restrict__ vel, double lambdt, int implicit,
+                                                           double *__restrict__ sums /* [rows][29] */) {
+  __shared__ double sm[kMomenta][65];
+  const int r = blockIdx.x;
+  const int k = constant(pl.row_obst)[r], b = constant(pl.row_block)[r];
+  const ObstItems it = plan_obstacle(pl, k);
+  Constant<double> *cm = constant(pl.body) + 9 * (size_t)k;
+  fluid_momenta_block(it, b, vel, lambdt, implicit, cm[0], cm[1], cm[2], sums + (size_t)r * kMomenta, sm);
+}
+
+__global__ void __launch_bounds__(256) k_penalize_set(PlanItems pl, double *__restrict__ vel, const double *__restrict__ chi_field, double dt, double lambdaFac,
+                                                       int implicit, double *__restrict__ forces /* [rows][6] */) {
+  __shared__ double red[4];
+  const int first = constant(pl.sched_first)[blockIdx.x], last = constant(pl.sched_first)[blockIdx.x + 1];
+  for (int e = first; e < last; ++e) {  // ascending obstacle index
+    const int r = constant(pl.sched_rows)[e];
+    const int k = constant(pl.row_obst)[r], i = constant(pl.row_block)[r];
+    const ObstItems it = plan_obstacle(pl, k);
+    Constant<double> *B = constant(pl.body) + 9 * (size_t)k;
+    penalize_block(it, i, vel, chi_field, dt, lambdaFac, implicit, B[0], B[1], B[2], B[3], B[4], B[5], B[6], B[7], B[8], forces + (size_t)r * 6, red);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_update_tmpv_set(PlanItems pl, double *__restrict__ tmpV, const double *__restrict__ chi_field) {
+  const int first = constant(pl.sched_first)[blockIdx.x], last = constant(pl.sched_first)[blockIdx.x + 1];
+  for (int e = first; e < last; ++e) {  // ascending obstacle index
+    const int r = constant(pl.sched_rows)[e];
+    const ObstItems it = plan_obstacle(pl, constant(pl.row_obst)[r]);
+    update_tmpv_block(it, constant(pl.row_block)[r], tmpV, chi_field);
+  }
+}
+
+namespace {
+
+// the retained set of a resident call of `nobst` obstacles, or why there is none
+int retained_for(Sim *s, const char *who, int nobst, RetainedObstacles **out) {
+  RetainedObstacles *R = s->retained;
+  if (!R) { set_error("%s: no cup3d_create_obstacles has left its blocks on the device", who); return CUP3D_ESTATE; }
+  if ((int)R->obst.size() != nobst) {
+    set_error("%s: %d obstacles, but cup3d_create_obstacles left %d", who, nobst, (int)R->obst.size());
+    return CUP3D_ESTATE;
+  }
+  *out = R;
+  return CUP3D_OK;
+}
+
+// the plan of the retained set, built on first use
+int resident_plan(Sim *s, RetainedObstacles *R, ResidentPlan **out) {
+  if (R->plan) { *out = R->plan; return CUP3D_OK; }
+  const size_t N = R->obst.size();
+  ResidentPlan *P = new ResidentPlan;
+  struct Drop { ResidentPlan *p; ~Drop() { delete p; } } drop{P};  // until it is handed over
+  P->row_base.assign(N + 1, 0);
+  for (size_t k = 0; k < N; ++k) P->row_base[k + 1] = P->row_base[k] + R->obst[k].nblocks;
+  P->rows = P->row_base[N];
+  if (P->rows > 0) {
+    const size_t nr = (size_t)P->rows;
+    std::vector<ObstItems> items(N);
+    std::vector<int32_t> row_obst(nr), row_block(nr), row_slot(nr), sched_rows(nr), sched_first;
+    for (size_t k = 0; k < N; ++k) {
+      const RetainedObstacles::One &o = R->obst[k];
+      items[k] = ObstItems{(const int32_t *)o.slots.p, (const double *)o.geom.p, (const double *)o.chi.p, (const double *)o.udef.p};
+      for (long i = 0; i < o.nblocks; ++i) {
+        const size_t r = (size_t)(P->row_base[k] + i);
+        row_obst[r] = (int32_t)k;
+        row_block[r] = (int32_t)i;
+        row_slot[r] = o.slots_h[i];
+      }
+    }
+    for (size_t r = 0; r < nr; ++r) sched_rows[r] = (int32_t)r;
+    // rows ascend with k, so a stable sort by slot leaves every slot's rows in ascending obstacle order
+    std::stable_sort(sched_rows.begin(), sched_rows.end(), [&](int32_t a, int32_t b) { return row_slot[a] < row_slot[b]; });
+    for (size_t e = 0; e < nr; ++e)
+      if (e == 0 || row_slot[sched_rows[e]] != row_slot[sched_rows[e - 1]]) sched_first.push_back((int32_t)e);
+    P->nslots = (long)sched_first.size();
+    sched_first.push_back((int32_t)nr);
+    int rc;
+    if ((rc = P->obst.upload(items.data(), N * sizeof(ObstItems))) || (rc = P->row_obst.upload(row_obst.data(), nr * sizeof(int32_t))) ||
+        (rc = P->row_block.upload(row_block.data(), nr * sizeof(int32_t))) || (rc = P->sched_first.upload(sched_first.data(), sched_first.size() * sizeof(int32_t))) ||
+        (rc = P->sched_rows.upload(sched_rows.data(), nr * sizeof(int32_t))) || (rc = P->body.alloc(N * 9 * sizeof(double))) ||
+        (rc = P->out.alloc(nr * kMomenta * sizeof(double))))
+      return rc;
+    CUP3D_HIP(hipStreamSynchronize(stream()));  // the tables are locals
+    P->bytes = P->obst.size + P->row_obst.size + P->row_block.size + P->sched_first.size + P->sched_rows.size + P->body.size + P->out.size;
+  }
+  drop.p = nullptr;
+  R->plan = P;
+  R->bytes += P->bytes;
+  s->bytes += P->bytes;
+  *out = P;
+  return CUP3D_OK;
+}
+
+PlanItems plan_items(const ResidentPlan *P) {
+  return PlanItems{(const ObstItems *)P->obst.p, (const int32_t *)P->row_obst.p, (const int32_t *)P->row_block.p, (const int32_t *)P->sched_first.p,
+                   (const int32_t *)P->sched_rows.p, (const double *)P->body.p};
+}
+
+}  // namespace
+
+}  // namespace cup3d
+
+extern "C" int cup3d_update_obstacles_resident(cup3d_sim_t *h, double dt, double lambda, int implicit, int nobst, cup3d_obstacle_body *body,
+                                               cup3d_obstacle_motion *motion) {
+  if (!h || nobst < 0 || !(dt > 0) || (nobst > 0 && (!body || !motion))) return CUP3D_EINVAL;
+  if (nobst == 0) return CUP3D_OK;
+  Sim *s = reinterpret_cast<Sim *>(h);
+  const int nq = implicit ? kMomenta : kMomentaExplicit;
+  const double lambdt = lambda * dt;  // 13664
+  // nothing of the caller's is written before every obstacle of the call has passed: the results wait here
+  std::vector<MomentaResult> res((size_t)nobst);
+  std::vector<double> rows, table;
+  DevBuf red;  // the all-reduce operand of this call: M[0..15] | M[16..28], error flag
+  if (scalars_cross_ranks(s)) {
+    int rc = red.alloc(32 * sizeof(double));
+    if (rc) return rc;
+  }
+  RetainedObstacles *R = nullptr;
+  // this rank's rows of every obstacle in one launch; what it gets wrong travels with the first obstacle's all-reduce
+  auto local_part = [&]() -> int {
+    int rc;
+    ResidentPlan *P;
+    if ((rc = retained_for(s, "cup3d_update_obstacles_resident", nobst, &R)) || (rc = resident_plan(s, R, &P))) return rc;
+    if (P->rows == 0) return CUP3D_OK;
+    table.assign(9 * (size_t)nobst, 0.0);
+    for (int k = 0; k < nobst; ++k)
+      for (int d = 0; d < 3; ++d) table[9 * (size_t)k + d] = body[k].cm[d];
+    CUP3D_HIP(hipMemcpyAsync(P->body.p, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
+    {
+      ProfileScope ps("update_obstacles_set");
+      hipLaunchKernelGGL(k_fluid_momenta_set, dim3((unsigned)P->rows), dim3(64), 0, stream(), plan_items(P), (const double *)s->vel, lambdt, implicit ? 1 : 0,
+                         (double *)P->out.p);
+    }
+    CUP3D_HIP(hipGetLastError());
+    rows.resize((size_t)P->rows * kMomenta);
+    CUP3D_HIP(hipMemcpyAsync(rows.data(), P->out.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    stats_field_download(rows.size() * sizeof(double));
+    return CUP3D_OK;
+  };
+  const int local = local_part();
+  for (int k = 0; k < nobst; ++k) {  // obstacles one after the other, as kernelFinalizeObstacleVel visits them (13739)
+    MomentaResult &Q = res[k];
+    for (int q = 0; q < kMomenta; ++q) Q.M[q] = 0.0;
+    // a rank that holds none of the obstacle's blocks still takes part in the all-reduce with M = 0 (MPI_Allreduce(M, 29), 13783)
+    if (!local && R->obst[k].nblocks > 0) {
+      Q.rows = rows.data() + (size_t)R->plan->row_base[k] * kMomenta;
+      Q.nblocks = R->obst[k].nblocks;
+      // kernelFinalizeObstacleVel's loop with one thread (13744-13781): block rows in block (slot) order
+      add_rows_in_slot_order(R->obst[k].slots_h.data(), Q.nblocks, Q.rows, kMomenta, nq, Q.M);
+    }
+    int rc = obstacle_motion_from_sums(s, "cup3d_update_obstacles_resident", k, local, (double *)red.p, implicit, motion[k], Q);
+    if (rc) return rc;
+  }
+  for (int k = 0; k < nobst; ++k) write_obstacle_motion(res[k], nq, motion[k], body[k].vel, body[k].omega);
+  return CUP3D_OK;
+}
+
+extern "C" int cup3d_penalization_resident(cup3d_sim_t *h, double dt, double lambda, int implicit, int nobst, cup3d_obstacle_body *body) {
+  if (!h || nobst < 0 || !(dt > 0) || (nobst > 0 && !body)) return CUP3D_EINVAL;
+  if (nobst == 0) return CUP3D_OK;
+  Sim *s = reinterpret_cast<Sim *>(h);
+  const double lambdaFac = implicit ? lambda : 1.0 / dt;  // 13867
+  std::vector<double> F, table;
+  RetainedObstacles *R = nullptr;
+  // every obstacle's blocks in one launch, slot by slot; what this rank gets wrong travels with the first obstacle's all-reduce
+  auto local_part = [&]() -> int {
+    int rc;
+    ResidentPlan *P;
+    if ((rc = retained_for(s, "cup3d_penalization_resident", nobst, &R)) || (rc = resident_plan(s, R, &P))) return rc;
+    if (P->rows == 0) return CUP3D_OK;
+    table.resize(9 * (size_t)nobst);
+    for (int k = 0; k < nobst; ++k)
+      for (int d = 0; d < 3; ++d) {
+        table[9 * (size_t)k + d] = body[k].cm[d];
+        table[9 * (size_t)k + 3 + d] = body[k].vel[d];
+        table[9 * (size_t)k + 6 + d] = body[k].omega[d];
+      }
+    CUP3D_HIP(hipMemcpyAsync(P->body.p, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
+    {
+      ProfileScope ps("penalization_set");
+      hipLaunchKernelGGL(k_penalize_set, dim3((unsigned)P->nslots), dim3(256), 0, stream(), plan_items(P), s->vel, (const double *)s->chi, dt, lambdaFac,
+                         implicit ? 1 : 0, (double *)P->out.p);
+    }
+    CUP3D_HIP(hipGetLastError());
+    F.resize((size_t)P->rows * 6);
+    CUP3D_HIP(hipMemcpyAsync(F.data(), P->out.p, F.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    stats_field_download(F.size() * sizeof(double));
+    return CUP3D_OK;
+  };
+  const int local = local_part();
+  std::vector<double> sums(7 * (size_t)nobst, 0.0);  // the caller's structs are written once every obstacle has passed
+  for (int k = 0; k < nobst; ++k) {  // as kernelFinalizePenalizationForce visits them; a rank without blocks of obstacle k adds zeros
+    double *M = &sums[7 * (size_t)k];
+    if (!local && R->obst[k].nblocks > 0)
+      add_rows_in_slot_order(R->obst[k].slots_h.data(), R->obst[k].nblocks, F.data() + (size_t)R->plan->row_base[k] * 6, 6, 6, M);
+    int rc = penalization_force_over_ranks(s, "cup3d_penalization_resident", k, local, M);
+    if (rc) return rc;
+  }
+  for (int k = 0; k < nobst; ++k) force_from_sums(&sums[7 * (size_t)k], body[k].force, body[k].torque);
+  return CUP3D_OK;
+}
+
+extern "C" int cup3d_update_tmpv_resident(cup3d_sim_t *h, int nobst) {
+  if (!h || nobst < 0) return CUP3D_EINVAL;
+  if (nobst == 0) return CUP3D_OK;
+  Sim *s = reinterpret_cast<Sim *>(h);
+  int rc;
+  RetainedObstacles *R;
+  ResidentPlan *P;
+  if ((rc = retained_for(s, "cup3d_update_tmpv_resident", nobst, &R)) || (rc = resident_plan(s, R, &P))) return rc;
+  if (P->rows > 0) {
+    ProfileScope ps("update_tmpv_set");
+    hipLaunchKernelGGL(k_update_tmpv_set, dim3((unsigned)P->nslots), dim3(256), 0, stream(), plan_items(P), s->tmpV, (const double *)s->chi);
+    CUP3D_HIP(hipGetLastError());
+  }
+  s->udef_nonzero = true;
   return CUP3D_OK;
 }
 

@@ -140,7 +140,8 @@ struct Sim {
   struct LabsView *labs_view = nullptr;  // cup3d_sim_labs_over_ranks: the rank's tensorial view, its tables, the ghost pool (amr.hip)
   struct ForcesScratch *forces = nullptr;  // cup3d_compute_forces: tile scratch and staged surface arrays, grow-only (obstacles.hip)
   // what the last successful cup3d_create_obstacles left on the device, per obstacle of that call: slots, geom, sdfLab, chi and the
-  // corrected udef -- what cup3d_prevent_colliding_obstacles reads (obstacles.hip); nullptr: nothing retained
+  // corrected udef -- what cup3d_prevent_colliding_obstacles and the resident operators (cup3d_*_resident) read, with the latter's plan
+  // once one of them has run (obstacles.hip); nullptr: nothing retained
   struct RetainedObstacles *retained = nullptr;
   int max_groups = 0;
   // staging for host transfers

@@ -514,6 +514,15 @@ def _obstacle_array(obstacles):
     return arr
 
 
+def _body_array(obstacles):
+    """cup3d_obstacle_body of every obstacle: the rigid state alone, for the operators that read the blocks CreateObstacles left on the device"""
+    arr = (capi.ObstacleBody * max(1, len(obstacles)))()
+    for o, a in zip(obstacles, arr):
+        for d in range(3):
+            a.cm[d], a.vel[d], a.omega[d] = o.cm[d], o.vel[d], o.omega[d]
+    return arr
+
+
 class ObstacleShape:
     """What the host's geometry leaves of one obstacle on this rank (Obstacle::create): the non-null ObstacleBlocks' slots, their signed
     distance sdf [n][10][10][10] (ObstacleBlock::sdfLab, index [z+1][y+1][x+1]) and deformation velocity udef [n][8][8][8][3], plus
@@ -591,21 +600,27 @@ class UpdateObstacles(Operator):
     """UpdateObstacles::operator()(dt), main.cpp:13812-13837, for sim.obstacles (ObstacleData list): KernelIntegrateFluidMomenta on the
     resident vel, then kernelFinalizeObstacleVel and Obstacle::computeVelocities without the collision override (cup3d_update_obstacles).
     Leaves in each ObstacleData the new vel / omega (what Penalization then penalises towards), vel_computed / omega_computed, totals
-    (M[29]) and block_sums [n][29].  A collective where the grid is spread over ranks."""
+    (M[29]) and block_sums [n][29].  A collective where the grid is spread over ranks.
+    With sim.resident_obstacles the blocks, chi and udef are those the last CreateObstacles left on the device
+    (cup3d_update_obstacles_resident): one launch for all obstacles, the same bits."""
 
     def __call__(self, dt):
         s = self.sim
         if not s.obstacles:
             return
         implicit = 1 if s.bImplicitPenalization else 0
-        arr = _obstacle_array(s.obstacles)
+        resident = getattr(s, "resident_obstacles", False)
+        arr = _body_array(s.obstacles) if resident else _obstacle_array(s.obstacles)
         mot = (capi.ObstacleMotion * len(s.obstacles))()
         sums = [np.zeros((len(o.slots), 29)) for o in s.obstacles]
         for o, m, b in zip(s.obstacles, mot, sums):
             for d in range(3):
                 m.forced[d], m.block_rotation[d], m.vel_imposed[d] = o.forced[d], o.block_rotation[d], o.vel_imposed[d]
             m.block_sums = b.ctypes.data
-        check(lib().cup3d_update_obstacles(s.handle, dt, s.lambda_penal, implicit, len(s.obstacles), arr, mot))
+        if resident:
+            check(lib().cup3d_update_obstacles_resident(s.handle, dt, s.lambda_penal, implicit, len(s.obstacles), arr, mot))
+        else:
+            check(lib().cup3d_update_obstacles(s.handle, dt, s.lambda_penal, implicit, len(s.obstacles), arr, mot))
         for o, a, m, b in zip(s.obstacles, arr, mot, sums):
             o.vel, o.omega = np.array(a.vel[:]), np.array(a.omega[:])
             o.vel_computed, o.omega_computed = np.array(m.vel_computed[:]), np.array(m.omega_computed[:])
@@ -655,8 +670,13 @@ class Penalization(Operator):
         s = self.sim
         if not s.obstacles:
             return
-        arr = _obstacle_array(s.obstacles)
-        check(lib().cup3d_penalization(s.handle, dt, s.lambda_penal, 1 if s.bImplicitPenalization else 0, len(s.obstacles), arr))
+        implicit = 1 if s.bImplicitPenalization else 0
+        if getattr(s, "resident_obstacles", False):   # on the blocks the last CreateObstacles left on the device: one launch, the same bits
+            arr = _body_array(s.obstacles)
+            check(lib().cup3d_penalization_resident(s.handle, dt, s.lambda_penal, implicit, len(s.obstacles), arr))
+        else:
+            arr = _obstacle_array(s.obstacles)
+            check(lib().cup3d_penalization(s.handle, dt, s.lambda_penal, implicit, len(s.obstacles), arr))
         for o, a in zip(s.obstacles, arr):
             o.force, o.torque = np.array(a.force[:]), np.array(a.torque[:])
 
@@ -775,7 +795,10 @@ class PressureProjection(Operator):
         s.dt = dt
         if s.obstacles:  # tmpV = 0; kernelUpdateTmpV (15066-15082): chi must be resident (sim.upload("chi", ...))
             s.fill("tmpV", 0.0)
-            check(lib().cup3d_update_tmpv(s.handle, len(s.obstacles), _obstacle_array(s.obstacles)))
+            if getattr(s, "resident_obstacles", False):
+                check(lib().cup3d_update_tmpv_resident(s.handle, len(s.obstacles)))
+            else:
+                check(lib().cup3d_update_tmpv(s.handle, len(s.obstacles), _obstacle_array(s.obstacles)))
         # every rank knows whether obstacles exist (the list is replicated, like the reference's obstacle_vector); chi placed by hand
         # without an ObstacleData list (tests) leaves the decision to the library
         by_hand = getattr(s, "_chi_uploaded", False) or getattr(s, "chi_resident", False)
@@ -821,13 +844,26 @@ class Simulation:
     """The time loop of struct Simulation restricted to the hot path (no obstacles, frozen mesh):
     calcMaxTimestep 15254-15305, advance 15306-15326, pipeline order of setupOperators 15229-15246."""
 
-    def __init__(self, sim, obstacle_operators=False, collisions=False):
+    def __init__(self, sim, obstacle_operators=False, collisions=False, resident_obstacles=False):
         """obstacle_operators: with sim.obstacles, put UpdateObstacles and Penalization between the forcing and PressureProjection
         (15235-15243) -- the resident obstacle step -- and, where sim.shapes is set (ObstacleShape list), CreateObstacles in front of
         everything.  Off by default: the caller then runs Penalization itself.
         collisions: with obstacle_operators, PreventCollidingObstacles directly in front of Penalization (14329); it needs the blocks
-        CreateObstacles leaves on the device, i.e. sim.shapes."""
+        CreateObstacles leaves on the device, i.e. sim.shapes.
+        resident_obstacles: with obstacle_operators, UpdateObstacles, Penalization and PressureProjection's tmpV update read the blocks, chi
+        and udef CreateObstacles leaves on the device instead of uploading them per obstacle (sets sim.resident_obstacles); the same
+        pipeline and the same bits.  It needs sim.shapes, so that CreateObstacles runs in front of them."""
+        if resident_obstacles and not (obstacle_operators and getattr(sim, "shapes", None)):
+            raise ValueError("resident_obstacles=True needs obstacle_operators=True and sim.shapes (an ObstacleShape list): the operators "
+                             "read the blocks CreateObstacles leaves on the device")
+        self._bind(sim, obstacle_operators, collisions, resident_obstacles)
+
+    def _bind(self, sim, obstacle_operators, collisions, resident_obstacles):
+        """the operators on `sim`: what __init__ does, and adaptMesh / adaptMeshOverRanks again on the adapted SimulationData"""
         self.sim, self.obstacle_operators, self.collisions = sim, bool(obstacle_operators), bool(collisions)
+        self.resident_obstacles = bool(resident_obstacles)
+        if self.resident_obstacles or hasattr(sim, "resident_obstacles"):
+            sim.resident_obstacles = self.resident_obstacles
         self.pipeline = [AdvectionDiffusionImplicit(sim) if sim.implicitDiffusion else AdvectionDiffusion(sim)]  # 15231-15234
         if sim.uMax_forced > 0:
             self.pipeline.append(ExternalForcing(sim))
@@ -848,7 +884,7 @@ class Simulation:
             GradChiOnTmp(s)(0)
         st = s.grid.valid_states(MeshAdaptation(Rtol, Ctol).Tag(s, "tmpV"))
         if (st != 0).any():
-            self.__init__(s.adapted(st), self.obstacle_operators, self.collisions)
+            self._bind(s.adapted(st), self.obstacle_operators, self.collisions, self.resident_obstacles)
         return st
 
     def adaptMeshOverRanks(self, mesh, owner, rank, nranks, Rtol, Ctol, allgather):
@@ -870,7 +906,7 @@ class Simulation:
         if not (st != 0).any():
             return st, mesh, owner
         new, new_mesh, new_owner = s.adapted_over_ranks(mesh, owner, st, rank, nranks)
-        self.__init__(new, self.obstacle_operators, self.collisions)
+        self._bind(new, self.obstacle_operators, self.collisions, self.resident_obstacles)
         return st, new_mesh, new_owner
 
     def calcMaxTimestep(self):

@@ -465,6 +465,45 @@ typedef struct {
  * i.e. BEFORE the projVel test, as written); *any = whether sim.bCollision was set */
 CUP3D_API int cup3d_prevent_colliding_obstacles(cup3d_sim_t *, double dt, int nobstacles, cup3d_obstacle_collision *obstacles,
                                                 int32_t *collided, int *ncollided, int *any);
+/* The three operators between AdvectionDiffusion and the Poisson solve on the RETAINED set: UpdateObstacles::operator() (13812-13837),
+ * Penalization::operator() without the collision model (14330-14340: KernelPenalization 13841-13912 and kernelFinalizePenalizationForce
+ * 13913-13938) and kernelUpdateTmpV (14948-14979, 15066-15085).  They compute, bit for bit, what cup3d_update_obstacles,
+ * cup3d_penalization and cup3d_update_tmpv compute from the chi and corrected udef that cup3d_create_obstacles returned -- but read them
+ * where that call left them on the device (see cup3d_prevent_colliding_obstacles), so no field byte goes up, nothing is allocated per
+ * call, and every operator is ONE launch and at most one download whatever the number of obstacles.  Obstacle k of a call is obstacle k of
+ * the last successful cup3d_create_obstacles: its blocks in the order listed there, its chi and corrected udef as that call left them.
+ *   The plan.  The first of the three to run after a cup3d_create_obstacles builds a plan of the retained set and keeps it with the set
+ *     (counted in cup3d_sim_device_bytes from then on, dropped with the set).  Row r = row_base[k] + i stands for block i of obstacle k;
+ *     with N obstacles, R rows and S distinct slots the plan holds N * (32 + 72) bytes (the obstacles' four array pointers; cm, vel, omega
+ *     of the call), R * (3 * 4 + 29 * 8) bytes (obstacle and block of a row, the slot-major list, the call's block rows) and (S + 1) * 4
+ *     bytes (where each slot's rows begin).  A rank with R = 0 holds an empty plan and launches nothing.
+ *   cup3d_update_obstacles_resident: KernelIntegrateFluidMomenta, one wavefront per row, cells in the reference's order; one download
+ *     of [R][29] doubles (cup3d_run_stats.field_bytes_downloaded); then per obstacle what cup3d_update_obstacles does on the host -- its
+ *     own code: rows added in ascending slot order, the all-reduce, the volume check, computeVelocities -- with motion[k].block_sums (may
+ *     be NULL) [retained nblocks][29] in the order the obstacle's blocks were listed.  body[k].cm is read, body[k].vel / omega written.
+ *   cup3d_penalization_resident: one workgroup per distinct slot walks the obstacles that hold the slot in ascending k and penalises
+ *     the slot's cells for each -- a thread keeps its two cells, so obstacle k + 1 sees what obstacle k wrote, the reference's order
+ *     (13849-13852); a block's six sums are reduced by the tree of cup3d_penalization.  One download of [R][6] doubles; force / torque as
+ *     kernelFinalizePenalizationForce adds them.  body[k].cm / vel / omega are read, force / torque written.
+ *   cup3d_update_tmpv_resident: the same schedule, tmpV += udef where chi <= the obstacle's chi, obstacle after obstacle.  No download.
+ *     Call after clearing tmpV and before cup3d_pressure_rhs / cup3d_pressure_project, like cup3d_update_tmpv.
+ * COLLECTIVE like the calls they stand for (cup3d_update_tmpv_resident is not): every rank calls with the same nobstacles; per obstacle,
+ * in obstacle order, two all-reduces of at most 16 values (29 totals and the flag) resp. one of 7 (6 sums and the flag); a rank that
+ * holds none of an obstacle's blocks takes part with zeros; a rank that fails -- nothing retained, say -- returns its own code, the
+ * others CUP3D_ECOMM, and every rank returns.
+ * CUP3D_EINVAL: a null handle, dt <= 0 or NaN, nobstacles < 0, null body / motion with nobstacles > 0, and -- after the all-reduce -- a
+ * total volume totals[0] <= DBL_EPSILON as in cup3d_update_obstacles.  CUP3D_ESTATE: no cup3d_create_obstacles has left its blocks on the
+ * device, or nobstacles differs from the retained count.  A refused call writes nothing of the caller's and launches nothing; nothing of
+ * the caller's is written before every obstacle of the call has passed.  nobstacles = 0 is a no-op. */
+typedef struct {
+  double cm[3], vel[3], omega[3];  /* in; vel / omega are written by cup3d_update_obstacles_resident */
+  double force[3], torque[3];      /* out of cup3d_penalization_resident */
+} cup3d_obstacle_body;
+CUP3D_API int cup3d_update_obstacles_resident(cup3d_sim_t *, double dt, double lambda, int implicit_penalization, int nobstacles,
+                                              cup3d_obstacle_body *bodies, cup3d_obstacle_motion *motion);
+CUP3D_API int cup3d_penalization_resident(cup3d_sim_t *, double dt, double lambda, int implicit_penalization, int nobstacles,
+                                          cup3d_obstacle_body *bodies);
+CUP3D_API int cup3d_update_tmpv_resident(cup3d_sim_t *, int nobstacles);
 /* ComputeForces::operator() without Obstacle::computeForces (main.cpp:12496-12503): KernelComputeForces::visit (12273-12493) on the
  * device.  One cup3d_obstacle_surface = the ObstacleBlocks of one Obstacle on this rank that have surface points (nPoints > 0; 12280
  * skips the others) with their surface_data as a CSR list: block i owns points [first[i], first[i+1]), ijk = surface_data::ix, iy, iz,

@@ -39,6 +39,20 @@
  *   timeops                wrap every entry of sim.pipeline in a wall-clock timer (after `hip ...`, if any); `op steps` then prints
  *                          `REF optime name=<class> calls=<n> seconds=<t>` per operator, plus calcMaxTimestep / adaptMesh (= the rest
  *                          of the step) -- the Amdahl split of a step with and without the drop-in (scripts/configs4_measure.py)
+ *   obst create <file>     (with -factory-content fish) CreateObstacles::operator() replayed statement by statement (13589-13621) with the
+ *                          reference's own update / create / KernelCharacteristicFunction / kernel*UdefMomenta, dumping in between: ids, sdfLab,
+ *                          udef; chi, mass and CoM rows, surface_data, the chi field; centre of mass; the 13 sums, mass, J, both corrections;
+ *                          the corrected udef
+ *   obst update <file>     UpdateObstacles::operator()(sim.dt): the 29 sums per ObstacleBlock, the obstacles' state before and after
+ *   obst collide <file>    Penalization::preventCollidingObstacles(): state before and after, bCollisionID, bCollision
+ *   obst penalize <file>   the rest of Penalization::operator()(sim.dt): KernelPenalization on sim.vel, every obstacle's force and torque
+ *   obst forces <file>     ComputeForces::operator()(sim.dt): per block with nPoints > 0 the 19 sums before, the 19 per-point arrays, the 19 sums
+ *   obst state <file> | obst loadstate <file>   every obstacle's rigid-body state and the clock (time, step, dt, uinf, coefU, lambda, nu,
+ *                          implicit flag) out / in: puts two binaries into the same state
+ *   obst run create|forces   the pipeline's CreateObstacles / ComputeForces entry once (the shim's, after `hip on` with CUP3D_HIP_CREATE=1 /
+ *                          CUP3D_HIP_FORCES=1); obst blocks <file>: what the ObstacleBlocks hold afterwards
+ *   obst motion <k> <u v w ox oy oz>   set transVel and angVel of obstacle k
+ *                          (all `obst` files are lists of named arrays: see Records below and oracle_lib.read_records)
  *   rep <n>                repeat every following `op` n times when timing
  * Every `op` prints one line `REF <op> seconds=<t> iters=<k> value=<v>`.
  */
@@ -169,6 +183,89 @@ std::vector<char> read_file(const std::string &path) {
   fclose(f);
   return b;
 }
+/* `obst ...`: a file of named arrays.  Per record: char name[48] (zero padded), int64 kind (0 = float64, 1 = int64), int64 count, then
+   count values of 8 bytes.  tests/oracle_lib.py:read_records reads it back into a dict. */
+struct Records {
+  std::vector<char> bytes;
+  void put(const std::string &name, long long kind, const void *p, size_t count) {
+    char head[48] = {0};
+    snprintf(head, sizeof head, "%s", name.c_str());
+    const long long n = (long long)count;
+    bytes.insert(bytes.end(), head, head + 48);
+    bytes.insert(bytes.end(), (const char *)&kind, (const char *)&kind + 8);
+    bytes.insert(bytes.end(), (const char *)&n, (const char *)&n + 8);
+    bytes.insert(bytes.end(), (const char *)p, (const char *)p + 8 * count);
+  }
+  void d(const std::string &name, const std::vector<double> &v) { put(name, 0, v.data(), v.size()); }
+  void d(const std::string &name, const double *p, size_t n) { put(name, 0, p, n); }
+  void i(const std::string &name, const std::vector<long long> &v) { put(name, 1, v.data(), v.size()); }
+  void write(const std::string &path) { write_file(path, bytes.data(), bytes.size()); }
+};
+/* an obstacle's rigid-body state: every member of Obstacle (main.cpp:7488-7552) the obstacle operators read or write, NSTATE doubles in
+   this order.  The collision velocities are uninitialised memory until a collision sets them (7547-7552): they travel as 0 while
+   collision_counter <= 0, where nothing reads them (13069). */
+constexpr int NSTATE = 85;
+std::vector<double> get_state(const Obstacle &o) {
+  std::vector<double> s;
+  auto a = [&](const Real *p, int n) { for (int k = 0; k < n; k++) s.push_back(p[k]); };
+  a(o.position, 3); a(o.absPos, 3); a(o.quaternion, 4); a(o.transVel, 3); a(o.angVel, 3);                                    /*  0..15 */
+  s.push_back(o.mass); s.push_back(o.length); a(o.J, 6); a(o.centerOfMass, 3);                                                /* 16..26 */
+  a(o.transVel_correction.data(), 3); a(o.angVel_correction.data(), 3);                                                       /* 27..32 */
+  a(o.old_position, 3); a(o.old_absPos, 3); a(o.old_quaternion, 4);                                                           /* 33..42 */
+  const bool c = o.collision_counter > 0;
+  s.push_back(o.collision_counter);                                                                                           /* 43 */
+  for (Real v : {o.u_collision, o.v_collision, o.w_collision, o.ox_collision, o.oy_collision, o.oz_collision}) s.push_back(c ? v : 0.0); /* 44..49 */
+  for (int k = 0; k < 3; k++) s.push_back(o.bForcedInSimFrame[k]);                                                            /* 50..52 */
+  for (int k = 0; k < 3; k++) s.push_back(o.bBlockRotation[k]);                                                               /* 53..55 */
+  for (int k = 0; k < 3; k++) s.push_back(o.bFixFrameOfRef[k]);                                                               /* 56..58 */
+  a(o.transVel_imposed.data(), 3);                                                                                            /* 59..61 */
+  s.push_back(o.penalM); a(o.penalCM.data(), 3); a(o.penalJ.data(), 6); a(o.penalLmom.data(), 3); a(o.penalAmom.data(), 3);  /* 62..77 */
+  a(o.transVel_computed.data(), 3); a(o.angVel_computed.data(), 3);                                                           /* 78..83 */
+  s.push_back(0.0);                                                                                                           /* 84: spare */
+  return s;
+}
+void set_state(Obstacle &o, const double *s) {
+  auto a = [&](Real *p, int n) { for (int k = 0; k < n; k++) p[k] = *s++; };
+  a(o.position, 3); a(o.absPos, 3); a(o.quaternion, 4); a(o.transVel, 3); a(o.angVel, 3);
+  o.mass = *s++; o.length = *s++; a(o.J, 6); a(o.centerOfMass, 3);
+  a(o.transVel_correction.data(), 3); a(o.angVel_correction.data(), 3);
+  a(o.old_position, 3); a(o.old_absPos, 3); a(o.old_quaternion, 4);
+  o.collision_counter = *s++;
+  o.u_collision = *s++; o.v_collision = *s++; o.w_collision = *s++; o.ox_collision = *s++; o.oy_collision = *s++; o.oz_collision = *s++;
+  for (int k = 0; k < 3; k++) o.bForcedInSimFrame[k] = *s++ != 0;
+  for (int k = 0; k < 3; k++) o.bBlockRotation[k] = *s++ != 0;
+  for (int k = 0; k < 3; k++) o.bFixFrameOfRef[k] = *s++ != 0;
+  a(o.transVel_imposed.data(), 3);
+  o.penalM = *s++; a(o.penalCM.data(), 3); a(o.penalJ.data(), 6); a(o.penalLmom.data(), 3); a(o.penalAmom.data(), 3);
+  a(o.transVel_computed.data(), 3); a(o.angVel_computed.data(), 3);
+}
+/* what the obstacle operators read of SimulationData: time, step, dt, dt_old, uinf[3], coefU[3], lambda, nu, bImplicitPenalization */
+std::vector<double> get_sim_state(const SimulationData &s) {
+  return {s.time, (double)s.step, s.dt, s.dt_old, s.uinf[0], s.uinf[1], s.uinf[2], s.coefU[0], s.coefU[1], s.coefU[2], s.lambda, s.nu,
+          (double)s.bImplicitPenalization};
+}
+/* the non-null ObstacleBlocks of one obstacle in blockID order */
+std::vector<long long> block_ids(const Obstacle &o) {
+  std::vector<long long> ids;
+  for (size_t b = 0; b < o.obstacleBlocks.size(); b++) if (o.obstacleBlocks[b]) ids.push_back((long long)b);
+  return ids;
+}
+void put_states(Records &R, SimulationData &sd, const std::string &tag) {
+  R.d(tag + "sim", get_sim_state(sd));
+  int k = 0;
+  for (const auto &o : sd.obstacle_vector->getObstacleVector()) R.d(tag + "o" + std::to_string(k++) + ".state", get_state(*o));
+}
+void put_chi_field(Records &R, SimulationData &sd, const std::string &name) {
+  std::vector<double> f(sd.chiInfo().size() * 512);
+  for (size_t i = 0; i < sd.chiInfo().size(); i++) memcpy(&f[i * 512], sd.chiInfo()[i].block, 4096);
+  R.d(name, f);
+}
+/* the 19 sums of ObstacleBlock::sumQoI (7289-7307) of one block */
+void qoi_of(ObstacleBlock *b, double *q) {
+  std::vector<Real> sum(ObstacleBlock::nQoI, 0);
+  b->sumQoI(sum);
+  for (int k = 0; k < ObstacleBlock::nQoI; k++) q[k] = sum[k];
+}
 } // namespace
 
 int main(int argc, char **argv) {
@@ -227,6 +324,11 @@ int main(int argc, char **argv) {
   for (auto &op : sd.pipeline)
     if (auto p = std::dynamic_pointer_cast<PressureProjection>(op)) proj = p;
   std::shared_ptr<Operator> hip_adv, hip_proj;
+  int idx_create = -1, idx_forces = -1; /* `obst run`: where setupOperators put CreateObstacles and ComputeForces (`hip on` replaces in place) */
+  for (size_t c = 0; c < sd.pipeline.size(); c++) {
+    if (std::dynamic_pointer_cast<CreateObstacles>(sd.pipeline[c])) idx_create = (int)c;
+    if (std::dynamic_pointer_cast<ComputeForces>(sd.pipeline[c])) idx_forces = (int)c;
+  }
 #ifdef CUP3D_WITH_HIP
   std::shared_ptr<cup3d_hip::DeviceMirror> hip_mirror;
 #define HIP_INVALIDATE() do { if (hip_mirror) hip_mirror->invalidate(); } while (0)
@@ -399,8 +501,8 @@ int main(int argc, char **argv) {
       if (buf.size() != total * per * 8) { fprintf(stderr, "loadb %s: size mismatch\n", fname.c_str()); exit(2); }
       for (size_t i = 0; i < F.infos->size(); i++) memcpy((*F.infos)[i].block, buf.data() + (first + i) * per * 8, per * 8);
     } else if (cmd == "obstacle") {
-      /* `obstacle <file>`: add ONE synthetic obstacle (the reference's own obstacles are fish whose geometry needs GSL): a
-         plain Obstacle whose ObstacleBlocks (7256-7263: chi[8][8][8], udef[8][8][8][3]) are read from the file together with its
+      /* `obstacle <file>`: add ONE synthetic obstacle with chi and udef of the test's choosing (the reference's own obstacles are
+         fish; they run here too, on the GSL stand-ins of refbuild/gsl: -factory-content and the `obst` commands): a plain Obstacle whose ObstacleBlocks (7256-7263: chi[8][8][8], udef[8][8][8][3]) are read from the file together with its
          rigid motion.  File: int64 n, int64 blockID[n], double chi[n][512], double udef[n][512][3], double cm[3], vel[3], omega[3].
          Everything downstream (KernelPenalization 13841-13912, kernelUpdateTmpV 14948-14979, KernelPressureRHS) is the
          reference's own code. */
@@ -431,6 +533,221 @@ int main(int argc, char **argv) {
         for (int d = 0; d < 3; d++) out.push_back(o->torque[d]);
       }
       write_file(path, out.data(), out.size() * 8);
+    } else if (cmd == "obst") {
+      /* the reference's own obstacles (fish, built with the GSL stand-ins of refbuild/gsl) through its own obstacle operators, with
+         what they leave written out as named arrays (Records above).  Obstacle k's arrays are called o<k>.<name>; arrays "per block"
+         list the obstacle's non-null ObstacleBlocks in blockID order (o<k>.ids). */
+      std::string sub, path; script >> sub >> path;
+      const auto &obstacles = sd.obstacle_vector->getObstacleVector();
+      Records R;
+      auto name = [](size_t k, const char *what) { return "o" + std::to_string(k) + "." + what; };
+      if (sub == "run") {
+        /* `obst run create|forces`: the entry of sim.pipeline that setupOperators filled with CreateObstacles (15230) / ComputeForces
+           (15244) -- after `hip on` with CUP3D_HIP_CREATE=1 / CUP3D_HIP_FORCES=1 the shim's operator sits there -- called once with sim.dt */
+        const int at = path == "create" ? idx_create : (path == "forces" ? idx_forces : -1);
+        if (at < 0) { fprintf(stderr, "obst run: no such pipeline entry: %s\n", path.c_str()); exit(2); }
+        Operator &entry = *sd.pipeline[at];
+        int status = 0;
+        char *cls = abi::__cxa_demangle(typeid(entry).name(), nullptr, nullptr, &status);
+        printf("REF obstrun entry=%s\n", status == 0 && cls ? cls : typeid(entry).name());   /* which operator ran: the test reads it */
+        free(cls);
+        entry(sd.dt);
+        continue;
+      } else if (sub == "blocks") {
+        /* `obst blocks <file>`: what the ObstacleBlocks hold now -- ids, chi, udef, the surface lists and, once ComputeForces has run,
+           the 19 per-point arrays (blocks with points, in blockID order) and every block's 19 sums -- and the obstacles' state */
+        for (size_t k = 0; k < obstacles.size(); k++) {
+          const auto ids = block_ids(*obstacles[k]);
+          std::vector<double> chi(ids.size() * 512), udef(ids.size() * 1536), dchi, delta, qoi(ids.size() * 19), flat;
+          std::vector<long long> first(1, 0), ijk;
+          std::vector<std::vector<double>> pts(19);
+          for (size_t i = 0; i < ids.size(); i++) {
+            ObstacleBlock *b = obstacles[k]->obstacleBlocks[ids[i]];
+            memcpy(&chi[i * 512], b->chi, 4096);
+            memcpy(&udef[i * 1536], b->udef, 1536 * 8);
+            for (const surface_data *p : b->surface) {
+              ijk.push_back(p->ix); ijk.push_back(p->iy); ijk.push_back(p->iz);
+              dchi.push_back(p->dchidx); dchi.push_back(p->dchidy); dchi.push_back(p->dchidz);
+              delta.push_back(p->delta);
+            }
+            first.push_back(first.back() + b->nPoints);
+            qoi_of(b, &qoi[i * 19]);
+            const Real *arrays[19] = {b->pX, b->pY, b->pZ, b->P, b->fX, b->fY, b->fZ, b->fxV, b->fyV, b->fzV, b->omegaX, b->omegaY, b->omegaZ,
+                                      b->vxDef, b->vX, b->vyDef, b->vY, b->vzDef, b->vZ};
+            if (b->filled) for (int a = 0; a < 19; a++) pts[a].insert(pts[a].end(), arrays[a], arrays[a] + b->nPoints);
+          }
+          for (int a = 0; a < 19; a++) flat.insert(flat.end(), pts[a].begin(), pts[a].end());
+          R.i(name(k, "ids"), ids); R.d(name(k, "chi"), chi); R.d(name(k, "udef"), udef); R.i(name(k, "first"), first); R.i(name(k, "ijk"), ijk);
+          R.d(name(k, "dchi"), dchi); R.d(name(k, "delta"), delta); R.d(name(k, "points"), flat); R.d(name(k, "qoi"), qoi);
+        }
+        put_states(R, sd, "");
+      } else if (sub == "motion") {
+        /* `obst motion <k> <u v w ox oy oz>`: transVel and angVel of obstacle k, e.g. two fish sent towards each other */
+        const size_t k = (size_t)std::stoul(path);
+        if (k >= obstacles.size()) { fprintf(stderr, "obst motion: no obstacle %zu\n", k); exit(2); }
+        for (int d = 0; d < 3; d++) script >> obstacles[k]->transVel[d];
+        for (int d = 0; d < 3; d++) script >> obstacles[k]->angVel[d];
+        continue;
+      } else if (sub == "state") {
+        put_states(R, sd, "");
+      } else if (sub == "loadstate") {
+        /* the file `obst state` wrote: puts this binary's obstacles and clock where another's were */
+        auto buf = read_file(path);
+        const size_t rec = 64, nsim = 13;
+        const char *q = buf.data() + rec;
+        const double *s = (const double *)q;
+        sd.time = s[0]; sd.step = (int)s[1]; sd.dt = s[2]; sd.dt_old = s[3];
+        for (int d = 0; d < 3; d++) { sd.uinf[d] = s[4 + d]; sd.coefU[d] = s[7 + d]; }
+        sd.lambda = s[10]; sd.nu = s[11]; sd.bImplicitPenalization = s[12] != 0;
+        q += nsim * 8;
+        for (const auto &o : obstacles) { set_state(*o, (const double *)(q + rec)); q += rec + NSTATE * 8; }
+        if (q != buf.data() + buf.size()) { fprintf(stderr, "obst loadstate: %s does not hold %zu obstacles\n", path.c_str(), obstacles.size()); exit(2); }
+      } else if (sub == "create") {
+        /* CreateObstacles::operator() (main.cpp:13589-13621) statement by statement, on one thread, with a dump between the statements */
+        put_states(R, sd, "in.");
+        sd.MeshChanged = false;                                                   /* 13594 */
+        std::vector<Info> &chiInfo = sd.chiInfo();
+        for (size_t i = 0; i < chiInfo.size(); ++i) ((ScalarBlock *)chiInfo[i].block)->clear();   /* 13597-13600 */
+        sd.uinf = sd.obstacle_vector->updateUinf();                               /* 13601 */
+        sd.obstacle_vector->update();                                             /* 13602 */
+        sd.obstacle_vector->create();                                             /* 13603 */
+        put_states(R, sd, "created.");
+        for (size_t k = 0; k < obstacles.size(); k++) {
+          const auto ids = block_ids(*obstacles[k]);
+          std::vector<double> sdf(ids.size() * 1000), udef(ids.size() * 1536);
+          for (size_t i = 0; i < ids.size(); i++) {
+            memcpy(&sdf[i * 1000], obstacles[k]->obstacleBlocks[ids[i]]->sdfLab, 8000);
+            memcpy(&udef[i * 1536], obstacles[k]->obstacleBlocks[ids[i]]->udef, 1536 * 8);
+          }
+          R.i(name(k, "ids"), ids); R.d(name(k, "sdf"), sdf); R.d(name(k, "udef"), udef);
+        }
+        {                                                                         /* 13605-13614 */
+          auto vecOB = sd.obstacle_vector->getAllObstacleBlocks();
+          const KernelCharacteristicFunction K(vecOB);
+          for (size_t i = 0; i < chiInfo.size(); ++i) K.operate(chiInfo[i], *(ScalarBlock *)chiInfo[i].block);
+        }
+        for (size_t k = 0; k < obstacles.size(); k++) {
+          const auto ids = block_ids(*obstacles[k]);
+          std::vector<double> chi(ids.size() * 512), com, dchi, delta;
+          std::vector<long long> first(1, 0), ijk;
+          for (size_t i = 0; i < ids.size(); i++) {
+            const ObstacleBlock *b = obstacles[k]->obstacleBlocks[ids[i]];
+            memcpy(&chi[i * 512], b->chi, 4096);
+            for (Real v : {b->mass, b->CoM_x, b->CoM_y, b->CoM_z}) com.push_back(v);
+            if ((int)b->surface.size() != b->nPoints) { fprintf(stderr, "obst create: surface.size() != nPoints\n"); exit(3); }
+            for (const surface_data *p : b->surface) {
+              ijk.push_back(p->ix); ijk.push_back(p->iy); ijk.push_back(p->iz);
+              dchi.push_back(p->dchidx); dchi.push_back(p->dchidy); dchi.push_back(p->dchidz);
+              delta.push_back(p->delta);
+            }
+            first.push_back(first.back() + b->nPoints);
+          }
+          R.d(name(k, "chi"), chi); R.d(name(k, "block_com"), com); R.i(name(k, "first"), first); R.i(name(k, "ijk"), ijk);
+          R.d(name(k, "dchi"), dchi); R.d(name(k, "delta"), delta);
+        }
+        put_chi_field(R, sd, "chi_field");
+        kernelComputeGridCoM(sd);                                                 /* 13616 */
+        for (size_t k = 0; k < obstacles.size(); k++) R.d(name(k, "cm"), obstacles[k]->centerOfMass, 3);
+        kernelIntegrateUdefMomenta(sd);                                           /* 13617 */
+        kernelAccumulateUdefMomenta(sd);                                          /* 13618 */
+        for (size_t k = 0; k < obstacles.size(); k++) {
+          const auto ids = block_ids(*obstacles[k]);
+          std::vector<double> rows;
+          for (long long id : ids) {
+            const ObstacleBlock *b = obstacles[k]->obstacleBlocks[id];
+            for (Real v : {b->V, b->FX, b->FY, b->FZ, b->TX, b->TY, b->TZ, b->J0, b->J1, b->J2, b->J3, b->J4, b->J5}) rows.push_back(v);
+          }
+          R.d(name(k, "block_momenta"), rows);
+          R.d(name(k, "mass"), &obstacles[k]->mass, 1); R.d(name(k, "J"), obstacles[k]->J, 6);
+          R.d(name(k, "transvel_correction"), obstacles[k]->transVel_correction.data(), 3);
+          R.d(name(k, "angvel_correction"), obstacles[k]->angVel_correction.data(), 3);
+        }
+        kernelRemoveUdefMomenta(sd);                                              /* 13619 */
+        for (size_t k = 0; k < obstacles.size(); k++) {
+          const auto ids = block_ids(*obstacles[k]);
+          std::vector<double> udef(ids.size() * 1536);
+          for (size_t i = 0; i < ids.size(); i++) memcpy(&udef[i * 1536], obstacles[k]->obstacleBlocks[ids[i]]->udef, 1536 * 8);
+          R.d(name(k, "udef_corrected"), udef);
+        }
+        sd.obstacle_vector->finalize();                                           /* 13620 */
+        put_states(R, sd, "out.");
+      } else if (sub == "update") {
+        /* UpdateObstacles::operator()(sim.dt), 13812-13837: the 29 sums per block (the sixteen G* are the constructor's zeros without
+           implicit penalisation) and the state going in and coming out */
+        put_states(R, sd, "in.");
+        UpdateObstacles op(sd);
+        op(sd.dt);
+        for (size_t k = 0; k < obstacles.size(); k++) {
+          std::vector<double> rows;
+          for (long long id : block_ids(*obstacles[k])) {
+            const ObstacleBlock *b = obstacles[k]->obstacleBlocks[id];
+            for (Real v : {b->V, b->FX, b->FY, b->FZ, b->TX, b->TY, b->TZ, b->J0, b->J1, b->J2, b->J3, b->J4, b->J5, b->GfX, b->GpX, b->GpY, b->GpZ,
+                           b->Gj0, b->Gj1, b->Gj2, b->Gj3, b->Gj4, b->Gj5, b->GuX, b->GuY, b->GuZ, b->GaX, b->GaY, b->GaZ}) rows.push_back(v);
+          }
+          R.d(name(k, "block_sums"), rows);
+        }
+        put_states(R, sd, "out.");
+      } else if (sub == "collide") {
+        /* Penalization::preventCollidingObstacles(), 14009-14324, through the pipeline's own Penalization */
+        std::shared_ptr<Penalization> pen;
+        for (auto &op : sd.pipeline) if (auto p = std::dynamic_pointer_cast<Penalization>(op)) pen = p;
+        if (!pen) { fprintf(stderr, "obst collide: no Penalization in the pipeline\n"); exit(2); }
+        put_states(R, sd, "in.");
+        pen->preventCollidingObstacles();
+        put_states(R, sd, "out.");
+        std::vector<long long> ids(sd.bCollisionID.begin(), sd.bCollisionID.end()), any(1, sd.bCollision ? 1 : 0);
+        R.i("collided", ids); R.i("bCollision", any);
+      } else if (sub == "penalize") {
+        /* Penalization::operator()(sim.dt) after the collision model, 14330-14340: KernelPenalization on every block, then the
+           obstacles' force and torque (o<k>.force6); `dump vel` shows what it did to the velocity */
+        put_states(R, sd, "in.");
+        const std::vector<Info> &ci = sd.chiInfo(), &vi = sd.velInfo();
+        KernelPenalization K(sd.dt, sd.lambda, sd.bImplicitPenalization, sd.obstacle_vector);
+        for (size_t i = 0; i < ci.size(); ++i) K(vi[i], ci[i]);
+        kernelFinalizePenalizationForce(sd);
+        for (size_t k = 0; k < obstacles.size(); k++)
+          R.d(name(k, "force6"), {obstacles[k]->force[0], obstacles[k]->force[1], obstacles[k]->force[2], obstacles[k]->torque[0], obstacles[k]->torque[1],
+                                  obstacles[k]->torque[2]});
+      } else if (sub == "forces") {
+        /* ComputeForces::operator(), 12496-12503: per obstacle the blocks with nPoints > 0 (o<k>.slots), their 19 sums before and after
+           and the 19 per-point arrays in the order of cup3d_obstacle_surface::points */
+        put_states(R, sd, "in.");
+        std::vector<std::vector<long long>> slots(obstacles.size());
+        for (size_t k = 0; k < obstacles.size(); k++) {
+          std::vector<double> before;
+          for (long long id : block_ids(*obstacles[k])) {
+            ObstacleBlock *b = obstacles[k]->obstacleBlocks[id];
+            if (b->nPoints == 0) continue;
+            slots[k].push_back(id);
+            before.resize(before.size() + 19);
+            qoi_of(b, &before[before.size() - 19]);
+          }
+          R.i(name(k, "slots"), slots[k]); R.d(name(k, "qoi_before"), before);
+        }
+        ComputeForces op(sd);
+        op(sd.dt);
+        for (size_t k = 0; k < obstacles.size(); k++) {
+          std::vector<double> after(slots[k].size() * 19);
+          std::vector<std::vector<double>> pts(19);
+          std::vector<long long> first(1, 0);
+          for (size_t i = 0; i < slots[k].size(); i++) {
+            ObstacleBlock *b = obstacles[k]->obstacleBlocks[slots[k][i]];
+            qoi_of(b, &after[i * 19]);
+            const Real *arrays[19] = {b->pX, b->pY, b->pZ, b->P, b->fX, b->fY, b->fZ, b->fxV, b->fyV, b->fzV, b->omegaX, b->omegaY, b->omegaZ,
+                                      b->vxDef, b->vX, b->vyDef, b->vY, b->vzDef, b->vZ};
+            for (int a = 0; a < 19; a++) pts[a].insert(pts[a].end(), arrays[a], arrays[a] + b->nPoints);
+            first.push_back(first.back() + b->nPoints);
+          }
+          std::vector<double> flat;
+          for (int a = 0; a < 19; a++) flat.insert(flat.end(), pts[a].begin(), pts[a].end());
+          R.i(name(k, "first"), first); R.d(name(k, "points"), flat); R.d(name(k, "qoi"), after);
+          const Obstacle &o = *obstacles[k];
+          R.d(name(k, "totals"), {o.surfForce[0], o.surfForce[1], o.surfForce[2], o.presForce[0], o.presForce[1], o.presForce[2], o.viscForce[0],
+                                  o.viscForce[1], o.viscForce[2], o.surfTorque[0], o.surfTorque[1], o.surfTorque[2], o.drag, o.thrust, o.Pout,
+                                  o.PoutBnd, o.defPower, o.defPowerBnd, o.pLocom});
+        }
+      } else { fprintf(stderr, "ref_tool: unknown obst command %s\n", sub.c_str()); exit(2); }
+      if (sub != "loadstate") R.write(path);
     } else if (cmd == "amrtol") {
       /* tolerance_for_refinement / tolerance_for_compression of the five MeshAdaptation objects
          (main.cpp:5037-5038); `amrtol -1 -2` makes every block refine, `amrtol 1e300 1e299` compress */

@@ -349,8 +349,8 @@ def amr_adapt_case(name, bpd, lmax, bc, passes, seed, qr=0.75, qc=0.4):
 
 def obstacle_cases():
     """KernelPenalization (+ force / torque), kernelUpdateTmpV inside PressureProjection and the chi-weighted right-hand side of
-    the reference, driven by a synthetic obstacle (oracle_lib.synthetic_obstacle; the reference's own obstacles are fish whose
-    geometry needs GSL).  One uniform grid and one multi-level mesh; stores the obstacle, the inputs and the outputs."""
+    the reference, driven by a synthetic obstacle (oracle_lib.synthetic_obstacle: chi and udef of the test's choosing on any mesh; the
+    reference's own fish run here too, on the GSL stand-ins of oracle/refbuild/gsl: fish_cases below).  One uniform grid and one multi-level mesh; stores the obstacle, the inputs and the outputs."""
     out = {}
     for name, implicit, lam in (("f16_mixed", 1, 1e6), ("amr_periodic_l01", 0, 1e4)):
         g = np.load(os.path.join(HERE, name + ".npz"))
@@ -384,6 +384,23 @@ def obstacle_cases():
                     name + "_pr_iters": [int(r["iters"]) for r in recs if r["op"] == "project"][0]})
         print(name, "obstacle blocks", len(obst["ids"]), "force", out[name + "_force6"][:3], "project iters", out[name + "_pr_iters"])
     np.savez_compressed(os.path.join(HERE, "obstacle_ops.npz"), **out)
+
+
+def fish_cases():
+    """The reference's own obstacles: StefanFish through CreateObstacles (statement by statement), UpdateObstacles, the collision model and
+    ComputeForces, by the harness's `obst` commands.  Recipes, array names and the split into fish_*_<part>.npz: tests/fish_cases.py."""
+    import fish_cases as F
+    for name in F.CASES:
+        d = F.run(name)
+        cov = F.parse_coverage(str(d["coverage"]))
+        assert all(int(cov[f"o{k}.blocks_with_points"]) >= 8 for k in range(F.nobstacles(name))), cov   # the fish still has a surface worth the name
+        if name == "fish_two_hit":
+            assert d["k.collided"].tolist() == [0, 1] and int(d["k.bCollision"][0]) == 1, "the reference reports no collision"
+            assert d["k2.collided"].tolist() == [0, 1] and cov["resolved_when_closing"] == "1,1,1,1,1"   # ... and resolves it once the two close in
+        if name == "fish_two_miss":
+            assert int(cov["shared_blocks"]) > 0 and d["k.collided"].size == 0 and int(d["k.bCollision"][0]) == 0
+        F.save(name, d)
+        print(str(d["coverage"]))
 
 
 def implicit_cases():
@@ -538,6 +555,9 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["mean3"]:   # one case only (added in round 3; the others regenerate identically)
         mean3_case()
         sys.exit(0)
+    if sys.argv[1:] == ["fish"]:   # the obstacle operators' fixtures only (the others regenerate identically)
+        fish_cases()
+        sys.exit(0)
     sfc_cases()
     adapt_cases()
     for c in AMR_CASES:
@@ -550,6 +570,7 @@ if __name__ == "__main__":
     vorticity_cases()
     grad_chi_cases()
     obstacle_cases()
+    fish_cases()
     implicit_cases()
     if O.have_ref_tool_mpi():
         partition_cases()

@@ -446,6 +446,16 @@ def have_ref_tool():
     return os.path.exists(REF_TOOL) and os.access(REF_TOOL, os.X_OK)
 
 
+def ref_tool_knows_obst(path=None):
+    """the binary exists and was built from a harness that has the `obst` commands (oracle/ref_harness.cpp); one built from an earlier
+    harness text -- a prebuilt oracle/_ref/ where the reference's sources cannot be read -- answers them with `unknown command`"""
+    path = path or REF_TOOL
+    if not (os.path.exists(path) and os.access(path, os.X_OK)):
+        return False
+    with open(path, "rb") as f:
+        return b"REF obstrun entry=" in f.read()
+
+
 def ref_args(bpd, level_max, level_start, extent, bc, nu=0.01, cfl=0.3, ic="taylorGreen", umax_forced=1.0,
              extra=()):
     a = ["-bpdx", bpd[0], "-bpdy", bpd[1], "-bpdz", bpd[2], "-levelMax", level_max, "-levelStart", level_start,
@@ -463,8 +473,11 @@ def run_ref(script_lines, args, threads=1, workdir=None, timeout=3600):
     with open(os.path.join(wd, "script.txt"), "w") as f:
         f.write("\n".join(script_lines) + "\n")
     env = dict(os.environ, OMP_NUM_THREADS=str(threads))
-    out = subprocess.run([REF_TOOL, "script.txt", "--"] + list(args), cwd=wd, env=env, check=True,
-                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout).stdout.decode()
+    try:
+        out = subprocess.run([REF_TOOL, "script.txt", "--"] + list(args), cwd=wd, env=env, check=True,
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout).stdout.decode()
+    except subprocess.CalledProcessError as e:   # say what the tool said: the exception's own text holds the command line only
+        raise RuntimeError(f"ref_tool left with status {e.returncode} in {wd}; its last words: {e.stderr.decode(errors='replace')[-2000:]}") from e
     recs = []
     for line in out.splitlines():
         if line.startswith("REF "):
@@ -515,6 +528,28 @@ def read_blocks(path, nb, ncomp):
     a = np.fromfile(path, dtype=np.float64)
     shape = (nb, 8, 8, 8, 3) if ncomp == 3 else (nb, 8, 8, 8)
     return a.reshape(shape)
+
+
+def read_records(path):
+    """A file of the harness's `obst` commands (oracle/ref_harness.cpp, Records): {name: float64 or int64 array}"""
+    raw = open(path, "rb").read()
+    out, at = {}, 0
+    while at < len(raw):
+        name = raw[at:at + 48].split(b"\0")[0].decode()
+        kind, n = np.frombuffer(raw, dtype=np.int64, count=2, offset=at + 48)
+        out[name] = np.frombuffer(raw, dtype=np.int64 if kind else np.float64, count=int(n), offset=at + 64).copy()
+        at += 64 + 8 * int(n)
+    return out
+
+
+def write_records(path, records):
+    """the inverse of read_records: records = [(name, array of float64 or of an integer type)]"""
+    with open(path, "wb") as f:
+        for name, a in records:
+            a = np.asarray(a)
+            kind = 0 if a.dtype == np.float64 else 1
+            f.write(name.encode().ljust(48, b"\0") + np.array([kind, a.size], dtype=np.int64).tobytes())
+            f.write(np.ascontiguousarray(a, dtype=np.float64 if kind == 0 else np.int64).tobytes())
 
 
 def read_tables(path):

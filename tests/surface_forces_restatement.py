@@ -1,7 +1,8 @@
 """KernelComputeForces::visit (main.cpp:12273-12493) restated in plain Python, line by line.  TEST INFRASTRUCTURE.
 
-The yardstick of k_surface_forces (cup3d_amd/csrc/obstacles.hip): no reference binary can run the functor (the reference's only
-obstacles are fish, whose geometry needs GSL), so it is written out here once more, from the reference's text and not from the kernel:
+The yardstick of k_surface_forces (cup3d_amd/csrc/obstacles.hip) on inputs of the tests' choosing (every path of the functor:
+tests/surface_forces_cases.py), written out once more from the reference's text and not from the kernel; the compiled reference runs the
+functor on its own fish, and this restatement equals it there bit for bit (tests/test_fish_fixtures.py, tests/golden/fish_one_*.npz):
 scalar float64 arithmetic (Python floats: IEEE doubles, no contraction) in the reference's association, `round` half away from zero,
 sums added point by point in order i = 0..nPoints-1.  It is evaluated on [-4,5) tensorial tiles -- the CPU oracle's
 (OracleMesh.labs(field, -4, 5, True), pinned bit for bit to the compiled reference) in the tests.

@@ -120,6 +120,43 @@ def test_fish_plumbing_run(tmp_path, mode):
     assert sum(h[5]) <= 1.3 * sum(c[5]) + 10, (h[5], c[5])
 
 
+@pytest.mark.timeout(300)
+@pytest.mark.skipif(not (O.ref_tool_knows_obst() and O.ref_tool_knows_obst(REF_HIP)), reason="oracle/_ref binaries built from a harness without the `obst` commands")
+def test_fish_create_and_forces_through_the_shim(tmp_path):
+    """CreateObstaclesHIP and ComputeForcesHIP (CUP3D_HIP_CREATE=1, CUP3D_HIP_FORCES=1) executed: the reference binary and the reference +
+    shim binary, one OpenMP thread each, get the fish_one command line (tests/fish_cases.py: the mesh after init is the fixture's), the
+    fixture's vel and pres (`loadb`) and the fixture's obstacle state and clock (`obst loadstate`), and each runs the CreateObstacles entry
+    and the ComputeForces entry of its pipeline once (`obst run`).  No solver sits in between, so everything the two operators leave in
+    the reference's own objects must be bit-equal: the chi field, every ObstacleBlock's chi and udef, the surface lists, the 19 per-point
+    arrays and the 19 sums, and the obstacle's state.  One launch of each binary: 0.46 s for the whole test on MI355X; the limit of 120 s per launch is to
+    test_fish_plumbing_run's 800 s (30 steps, hundreds of solver iterations each) what two operator calls are to that."""
+    import fish_cases as F
+    d = F.load("fish_one")
+    nb = len(d["tables"])
+    script = ["tables t.bin", "loadb vel v.bin", "loadb pres p.bin", "obst loadstate s.bin", "obst run create", "obst run forces", "obst blocks b.bin",
+              "dump chi c.bin"]
+    res = {}
+    for tag, tool, pre, env in (("cpu", O.REF_TOOL, [], {}), ("hip", REF_HIP, ["hip on"], {"CUP3D_HIP_CREATE": "1", "CUP3D_HIP_FORCES": "1"})):
+        wd = tmp_path / tag
+        wd.mkdir()
+        np.ascontiguousarray(d["vel"]).tofile(str(wd / "v.bin"))
+        np.ascontiguousarray(d["pres"]).tofile(str(wd / "p.bin"))
+        O.write_records(str(wd / "s.bin"), [("sim", d["c.in.sim"]), ("o0.state", d["c.in.o0.state"])])
+        with open(str(wd / "script.txt"), "w") as f:
+            f.write("\n".join(pre + script) + "\n")
+        out = subprocess.run([tool, "script.txt", "--"] + F.ref_args("fish_one"), cwd=str(wd), env=dict(os.environ, OMP_NUM_THREADS="1", **env), check=True,
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120).stdout.decode()
+        ran = [l.split("entry=")[1] for l in out.splitlines() if l.startswith("REF obstrun")]   # the operators `obst run` found in the pipeline
+        assert ran == (["cup3d_hip::CreateObstaclesHIP", "cup3d_hip::ComputeForcesHIP"] if tag == "hip" else ["CreateObstacles", "ComputeForces"]), ran
+        assert np.array_equal(O.read_tables(str(wd / "t.bin"))[0], d["tables"])
+        res[tag] = dict(O.read_records(str(wd / "b.bin")), chi_field=O.read_blocks(str(wd / "c.bin"), nb, 1))
+    c, h = res["cpu"], res["hip"]
+    assert sorted(c) == sorted(h)
+    assert c["o0.first"][-1] > 500 and np.abs(c["o0.points"]).max() > 0 and np.abs(c["o0.qoi"]).max() > 0 and (c["chi_field"] > 0).sum() > 100
+    for k in sorted(c):
+        assert c[k].shape == h[k].shape and np.array_equal(c[k], h[k]), f"{k}: {int((c[k] != h[k]).sum())} of {c[k].size} entries differ"
+
+
 def test_poisson_solver_through_the_factory_key(tmp_path):
     """-poissonSolver cuda_iterative: the slot makePoissonSolver (main.cpp:14747-14758) reserves for a GPU solver, filled by
     cup3d_hip::makePoissonSolver; PoissonSolverBase::solve() contract: right-hand side in sim.lhs, initial guess and result in

@@ -1,6 +1,7 @@
 """The C++ shim (cup3d_amd/host/cup3d_hip_operators.h) with CreateObstaclesHIP compiles and links into the unmodified reference TU against
-a REAL <mpi.h>, and the binary refers to the entry point of the device operator.  The operator itself cannot be executed here: the
-reference's only obstacles are fish, whose geometry needs GSL, and the harness's synthetic obstacle has no signed distance.  Needs the
+a REAL <mpi.h>, and the binary refers to the entry point of the device operator.  A link check of the multi-rank branch only: the
+operator is EXECUTED, on the reference's own fish (which run on the GSL stand-ins of oracle/refbuild/gsl), by
+tests/test_gpu_dropin.py::test_fish_create_and_forces_through_the_shim.  Needs the
 reference sources and the build container's MPICH: skipped elsewhere, as tests/test_shim_forces_builds.py is (the GPU box only uses prebuilt
 files)."""
 import os

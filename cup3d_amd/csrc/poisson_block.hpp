@@ -9,8 +9,8 @@ namespace cup3d {
 // registers; z-neighbours come from registers, x/y-neighbours from an LDS copy of p with
 // zero rows above and below (the zero Dirichlet halo of the reference's PaddedBlock).
 // Two wave reductions per CG iteration (p.Ap and r.r).
-// FMA = contract a*b+c where the reference has a separate multiply and add (tuning variant
-// only: the production launch keeps the reference's association).
+// FMA = contract a*b+c where the reference has a separate multiply and add: the production
+// launch (block_solver 0); block_solver 2 keeps the reference's association (see launch_precond).
 template <bool FMA>
 __device__ __forceinline__ double mad(double a, double b, double c) {
   if constexpr (FMA) return __builtin_fma(a, b, c);

@@ -323,18 +323,117 @@ __device__ __forceinline__ void loop2_cg_body(const GridDev &g, const Vecs &V, c
 // are spilled, outside the CG loop) -> 5 wavefronts per SIMD: 3.63-3.70 ms instead of 3.75 at 512^3, 0.457-0.461 instead of 0.497 at
 // 256^3 (profiles/r02/probe_fused_kernel_occupancy.jsonl).  The same test on the other side -- the first kernel or the stand-alone block
 // CG held to 80 registers for 6 wavefronts -- loses (12-14 spills inside the loops: 5.3 ms instead of 3.88; CG 0.43 instead of 0.40).
-// (With FLHS held to 96 it spills 30 registers inside the plane loop: the production kernel of uniform grids is k_loop2_cg_w4 below.)
+// (With FLHS held to 96 it spills 30 registers inside the plane loop: uniform grids take k_loop2_cg_w4 / k_loop2_cg_w5 below.)
 template <bool FMA, int EV, bool FLHS>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
 k_loop2_cg(GridDev g, Vecs V, const SolverCtl *__restrict__ ctl, double *block_dots, long nb, double *block_sums, int *__restrict__ iters_out, LhsIn L, const LoopSums *__restrict__ Z) {
   loop2_cg_body<FMA, EV, FLHS>(g, V, ctl, block_dots, nb, block_sums, iters_out, L, Z);
 }
-// PRODUCTION on uniform grids (FLHS = true; what bench.py's `value` runs): the register allocation the compiler picks on its own, 128
-// registers -> 4 wavefronts per SIMD, no spills.  (Also the "loop2_four_waves" A/B of the FLHS = false form.)
+// Uniform grids (FLHS = true), launches below kLoop2FiveWavesFrom blocks and the reference's association (block_solver 2): the register
+// allocation the compiler picks on its own, 128 registers -> 4 wavefronts per SIMD, no spills.  PRODUCTION until k_loop2_cg_w5 (below) took
+// over the large launches.  (Also the "loop2_four_waves" A/B of the FLHS = false form.)
 template <bool FMA, int EV, bool FLHS>
 __global__ void __launch_bounds__(64) k_loop2_cg_w4(GridDev g, Vecs V, const SolverCtl *__restrict__ ctl, double *block_dots, long nb, double *block_sums,
                                                     int *__restrict__ iters_out, LhsIn L, const LoopSums *__restrict__ Z) {
   loop2_cg_body<FMA, EV, FLHS>(g, V, ctl, block_dots, nb, block_sums, iters_out, L, Z);
+}
+
+// The second loop with the LHS inside at 5 wavefronts per SIMD (FLHS = true, block CG, per-block sums totalled by k_sums_finish: the form
+// production launches on uniform grids).  loop2_cg_body held to 96 registers spills 124 B per lane inside the plane loop, so this is a
+// body of its own: the same arithmetic per cell in the same order, the same stores, the same per-block sums -- every vector is the same
+// bits as k_loop2_cg_w4's -- in 88 registers without scratch.  (A copy, not a helper shared with loop2_cg_body: an edit to that body moves
+// the pinned allocation of the four kernels built from it, and helpers move it too -- see the note above loop1_cg_body.)
+//  * Where the registers went: nothing but the tail reads the six running sums, so the optimiser SINKS their multiply-adds out of the
+//    plane loop to behind it -- and keeps r0, s, z, rv and w of all eight planes alive for that (the spills, and a vmcnt(0) wait in front
+//    of each).  An empty asm that names the six sums at the end of every plane makes them values the plane has to produce: the loop
+//    then holds two planes of streams, r[] and the sums, as written.  (Making the lane offset opaque per plane, a scheduling barrier per plane and
+//    r[] parked in the dead tile plane were tried on top: 88, 88 and 84 registers, none needed; every load takes scalar base + one
+//    32-bit lane offset as it is.)
+//  * No wave-priority branches (production runs kLoopPrio = 0).
+template <bool FMA, int EV>
+__device__ __forceinline__ void loop2_cg5_body(const GridDev &g, const Vecs &V, const SolverCtl *__restrict__ ctl, double *block_dots, long nb,
+                                               double *block_sums, int *__restrict__ iters_out, const LhsIn &L) {
+  __shared__ double P[kTileLds];
+  const int slot = block_slot(g);
+  if (slot < 0) return;
+  if (ctl->state != kRun) return;
+  const Loop2Args a{ctl->alpha, ctl->omega};
+  const int xc = ctl->xcur, xw = ctl_xwrite(*ctl);
+  const double *const xin = xc ? V.v[XOPT] : V.v[X_];
+  const int l = threadIdx.x;
+  const double hq = block_h(g, slot), invh = 1 / hq;
+  double r[8], acc[6] = {0, 0, 0, 0, 0, 0};
+  const size_t bo = (size_t)slot * 512;
+  // zhat comes from the tile and v is computed from it: ten streams are loaded
+  enum { iQHAT, iY, iR0, iX, iPHAT, iQ, iWHAT, iT, iS, iZ, NS };
+  const double *const src[NS] = {V.v[QHAT] + bo, V.v[Y_] + bo, V.v[R0] + bo, xin + bo, V.v[PHAT] + bo, V.v[Q_] + bo, V.v[WHAT] + bo, V.v[T_] + bo,
+                                 V.v[S_] + bo, V.v[Z_] + bo};
+  double *const oX = (xw ? V.v[XOPT] : V.v[X_]) + bo, *const oR = V.v[R_] + bo, *const oRH = V.v[RHAT] + bo, *const oW = V.v[W_] + bo, *const oV = V.v[V_] + bo;
+  double in[2][NS];
+  // (the lane's part of the address as a 32-bit BYTE offset: with the element index the offset is widened to 64 bits per stream and
+  //  the kernel is back at 96 registers and 12 B of scratch)
+#define LOAD_PLANE(buf, off)                                                                      \
+  {                                                                                               \
+    const unsigned o = (unsigned)(off) * 8u;                                                      \
+    _Pragma("unroll") for (int i = 0; i < NS; ++i)                                                \
+      in[buf][i] = __builtin_nontemporal_load((const double *)((const char *)src[i] + o));        \
+  }
+  // the tile's loads first, the first plane of the streams right behind them, then the tile goes to LDS
+  const LhsFix fx = lhs_fix(L, ctl, slot, l, hq);
+  TileRegs tr;
+  tile_issue_own(slot, V.v[ZHAT], l, tr);
+  const TileIdx ix = tile_idx(l);
+  LOAD_PLANE(0, l)
+  tile_issue_faces(g, slot, V.v[ZHAT], L.halo, l, tr);
+  tile_commit(tr, P, l);
+#pragma unroll
+  for (int zz = 0; zz < 8; ++zz) {  // second fused loop, 14503-14515
+    const int j = zz * 64 + l;
+    if (zz < 7) { LOAD_PLANE((zz + 1) & 1, j + 64) }
+    const double *c = in[zz & 1];
+    double zhat;
+    const double v = zz == 0 ? tile_lhs<0>(P, ix, zhat, hq, fx) : tile_lhs<1>(P + (zz - 1) * kTilePitch, ix, zhat, hq, fx);   // v = A zhat, 14489
+    NTS(oV, j, v);                                                                // the next first loop streams it
+    const double qhat = c[iQHAT], y = c[iY], r0 = c[iR0];
+    const double x = c[iX] + a.alpha * c[iPHAT] + a.omega * qhat;
+    const double rv = c[iQ] - a.omega * y;
+    const double rhat = qhat - a.omega * (c[iWHAT] - a.alpha * zhat);
+    const double w = y - a.omega * (c[iT] - a.alpha * v);
+    NTS(oX, j, x); NTS(oR, j, rv); NTS(oRH, j, rhat); NTS(oW, j, w);
+    acc[0] += r0 * rv;
+    acc[1] += r0 * w;
+    acc[2] += r0 * c[iS];
+    acc[3] += r0 * c[iZ];
+    acc[4] += rv * rv;   // norm_1
+    acc[5] += r0 * r0;   // norm_2
+    r[zz] = invh * w;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) asm volatile("" : "+v"(acc[i]));  // this plane's sums are formed HERE (see above); no instruction
+  }
+#undef LOAD_PLANE
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const double t = wave_sum(acc[i]);
+    if (l == 0) block_dots[(size_t)i * nb + slot] = t;
+    if (i == 4 && l == 0) block_dots[(size_t)6 * nb + slot] = t;  // norm = the same sum as norm_1 (14512-14514)
+  }
+  __syncthreads();  // the tile is read no more: the block solve takes over its LDS
+  cg_block<FMA, false, EV>(g, slot, r, V.v[WHAT], block_sums, 0.0, 0.0, iters_out, P);  // what = M^-1 w, 14548
+}
+// PRODUCTION on uniform grids (what bench.py's `value` runs) for launches of >= kLoop2FiveWavesFrom blocks; below that k_loop2_cg_w4.
+// Measured, one box, k_loop2_cg_w5 against k_loop2_cg_w4 (profiles/loop2_five_waves/): release libraries of the parent commit and of this
+// one, five alternating runs of the driver's command at 512^3: 3.699-3.712 against 3.844-3.879 ms (median -4.2 %; the iteration
+// 8.055-8.085 against 8.174-8.204 ms, -1.45 %: the first loop kernel behind it takes 3.72-3.73 instead of 3.68-3.69).  The threshold scan
+// (testing build, `loop2_five_waves` 1 against 2, two passes): 384^3 (110 592 blocks) 1.520-1.523 against 1.606-1.609 ms; 320^3 (64 000)
+// 0.873-0.874 against 0.918-0.919; 256^3 (32 768) 0.444-0.445 against 0.468-0.469; 192^3 (13 824) 0.201 against 0.209; 128^3 (4 096 blocks =
+// one round of wavefronts at either occupancy) 0.080 against 0.081-0.082, the iteration 0.230-0.232 either way.  Unlike the first kernel
+// there is no crossover: the threshold is the smallest launch at which the gain is outside the run-to-run range.
+constexpr int kLoop2FiveWavesFrom = 13824;
+template <bool FMA, int EV, bool FLHS>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
+k_loop2_cg_w5(GridDev g, Vecs V, const SolverCtl *__restrict__ ctl, double *block_dots, long nb, double *block_sums, int *__restrict__ iters_out, LhsIn L, const LoopSums *__restrict__ Z) {
+  static_assert(FLHS, "the five-wavefront form of the second loop has the LHS inside");
+  loop2_cg5_body<FMA, EV>(g, V, ctl, block_dots, nb, block_sums, iters_out, L);
 }
 
 // The two kernels of an iteration with the totals INSIDE (TOT; uniform grids, block CG): the early all-reduce over ranks (solve(): `early`).
@@ -375,6 +474,8 @@ static LoopKernel loop_kernel(int which, int block_solver, bool own_lhs, bool ea
     const int five = debug_option("loop1_five_waves");  // 1 = always, 2 = never
     if (which == 1 && own_lhs && five) return five == 1 ? k_loop1_cg_w5<true, P, true> : k_loop1_cg<true, P, true>;
     if (which == 2 && !own_lhs && debug_option("loop2_four_waves")) return k_loop2_cg_w4<true, P, false>;
+    const int five2 = debug_option("loop2_five_waves");  // 1 = always, 2 = never
+    if (which == 2 && own_lhs && five2) return five2 == 1 ? k_loop2_cg_w5<true, P, true> : k_loop2_cg_w4<true, P, true>;
   }
 #endif
   const bool fma = block_solver == 0;  // the production block CG; else (block_solver 2) the reference's association
@@ -384,11 +485,12 @@ static LoopKernel loop_kernel(int which, int block_solver, bool own_lhs, bool ea
     if (!own_lhs) return k_loop1_cg<true, P, false>;
     return nblocks >= kFiveWavesFrom ? k_loop1_cg_w5<true, P, true> : k_loop1_cg<true, P, true>;
   }
-  // with the LHS inside, the second loop asks for 128 registers: 4 wavefronts per SIMD without spills (k_loop2_cg_w4; held to 96 it
-  // spills 30 registers inside the plane loop), and the 7.5 KB tile needs 16 wavefronts per CU or fewer anyway
+  // with the LHS inside, loop2_cg_body asks for 128 registers: 4 wavefronts per SIMD without spills (k_loop2_cg_w4; held to 96 it
+  // spills 30 registers inside the plane loop); the production launch has a body of its own that fits 5 (k_loop2_cg_w5)
   if (early) return fma ? k_loop2_cg_tot<true, P> : k_loop2_cg_tot<false, 0>;
   if (!fma) return own_lhs ? k_loop2_cg_w4<false, 0, true> : k_loop2_cg<false, 0, false>;
-  return own_lhs ? k_loop2_cg_w4<true, P, true> : k_loop2_cg<true, P, false>;
+  if (!own_lhs) return k_loop2_cg<true, P, false>;
+  return nblocks >= kLoop2FiveWavesFrom ? k_loop2_cg_w5<true, P, true> : k_loop2_cg_w4<true, P, true>;
 }
 
 }  // namespace cup3d

@@ -138,10 +138,10 @@ struct Sim {
   void *mg = nullptr;              // level hierarchy of the multigrid preconditioner (multigrid.hip), built on first use
   struct LabTables *labs = nullptr;  // tables and staging buffer of cup3d_sim_labs (amr.hip), built on first use
   struct LabsView *labs_view = nullptr;  // cup3d_sim_labs_over_ranks: the rank's tensorial view, its tables, the ghost pool (amr.hip)
-  struct ForcesScratch *forces = nullptr;  // cup3d_compute_forces: tile scratch and staged surface arrays, grow-only (obstacles.hip)
+  struct ForcesScratch *forces = nullptr;  // cup3d_compute_forces: tile scratch and staged surface arrays, grow-only (obstacles_forces.hip)
   // what the last successful cup3d_create_obstacles left on the device, per obstacle of that call: slots, geom, sdfLab, chi and the
   // corrected udef -- what cup3d_prevent_colliding_obstacles and the resident operators (cup3d_*_resident) read, with the latter's plan
-  // once one of them has run (obstacles.hip); nullptr: nothing retained
+  // once one of them has run (obstacles.hpp, obstacles_create.hip); nullptr: nothing retained
   struct RetainedObstacles *retained = nullptr;
   int max_groups = 0;
   // staging for host transfers
@@ -238,8 +238,8 @@ int launch_mean_total(Sim *s);  // total of the block sums in d_partials' tail -
 int mg_vcycle(Sim *s, const double *in, double *out);
 void mg_destroy(Sim *s);
 void labs_destroy(Sim *s);  // what cup3d_sim_labs and cup3d_sim_labs_over_ranks built on first use (amr.hip)
-void forces_destroy(Sim *s);  // the scratch of cup3d_compute_forces (obstacles.hip)
-void retained_destroy(Sim *s);  // the obstacle blocks cup3d_create_obstacles keeps (obstacles.hip)
+void forces_destroy(Sim *s);  // the scratch of cup3d_compute_forces (obstacles_forces.hip)
+void retained_destroy(Sim *s);  // the obstacle blocks cup3d_create_obstacles keeps (obstacles_create.hip)
 // implicit diffusion (DiffusionSolver, main.cpp:6719-7147): Helmholtz operator of velocity component `direction`
 struct HelmholtzOp { int direction; double dt, nu; };
 int launch_lhs_diffusion(Sim *s, const double *p, double *out, const HelmholtzOp &op);

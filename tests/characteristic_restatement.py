@@ -1,7 +1,7 @@
 """The grid half of CreateObstacles::operator() (main.cpp:13596-13619) restated in plain Python, line by line.  TEST INFRASTRUCTURE.
 
 The yardstick of cup3d_create_obstacles (k_characteristic, k_udef_momenta, k_remove_udef_momenta and the host half,
-cup3d_amd/csrc/obstacles.hip), written from the reference's text and not from the kernels: scalar float64 arithmetic (Python floats: IEEE
+cup3d_amd/csrc/obstacles_create.hip), written from the reference's text and not from the kernels: scalar float64 arithmetic (Python floats: IEEE
 doubles, no contraction) in the reference's association.
 
   characteristic   KernelCharacteristicFunction::operate (13298-13403) for one ObstacleBlock: chi, the max into the block of the chi

@@ -1,7 +1,7 @@
 """Penalization::preventCollidingObstacles (main.cpp:14009-14323) with ComputeJ and ElasticCollision (13939-14007) restated in plain
 Python, line by line.  TEST INFRASTRUCTURE.
 
-The yardstick of cup3d_prevent_colliding_obstacles (k_collision_sums and the host half, cup3d_amd/csrc/obstacles.hip), written from the
+The yardstick of cup3d_prevent_colliding_obstacles (k_collision_sums and the host half, cup3d_amd/csrc/obstacles_collisions.hip), written from the
 reference's text and not from the kernel: scalar float64 arithmetic (Python floats: IEEE doubles, no contraction, math.sqrt correctly
 rounded) in the reference's association.
 

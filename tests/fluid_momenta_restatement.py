@@ -1,6 +1,6 @@
 """UpdateObstacles::operator() (main.cpp:13812-13837) restated in plain Python, line by line.  TEST INFRASTRUCTURE.
 
-The yardstick of cup3d_update_obstacles (k_fluid_momenta and the host half, cup3d_amd/csrc/obstacles.hip), written from the reference's
+The yardstick of cup3d_update_obstacles (k_fluid_momenta and the host half, cup3d_amd/csrc/obstacles_update.hip), written from the reference's
 text and not from the kernel: scalar float64 arithmetic (Python floats: IEEE doubles, no contraction) in the reference's association.
 
   block_sums   KernelIntegrateFluidMomenta<0/1>::visit (13637-13734): the 29 sums of one ObstacleBlock, cells in iz, iy, ix order,

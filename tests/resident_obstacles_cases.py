@@ -3,10 +3,10 @@ cup3d_update_tmpv_resident) and a short NumPy statement of what order means to t
 
 The meshes and the spheres A, B, C of tests/collision_cases.py; every sphere lists every block, B's list descends.  The GPU tests compare
 the resident entry points with the staged ones bit for bit, so nothing here has to reproduce the device's bits: `penalize` and
-`update_tmpv` state the per-cell rules of k_penalize / k_update_tmpv (csrc/obstacles.hip; KernelPenalization, main.cpp:13841-13912, and
+`update_tmpv` state the per-cell rules of k_penalize / k_update_tmpv (csrc/obstacles_penalization.hip; KernelPenalization, main.cpp:13841-13912, and
 kernelUpdateTmpV, 14948-14979) so that tests/test_resident_obstacles_cases.py can count where the order of the obstacles shows: a
 slot-major kernel that visits a slot's obstacles in another order than the staged calls' cannot give the same bits there.
-`plan` restates the plan of the retained set (ResidentPlan, csrc/obstacles.hip)."""
+`plan` restates the plan of the retained set (ResidentPlan, csrc/obstacles.hpp)."""
 import numpy as np
 
 import collision_cases as K

@@ -1,6 +1,6 @@
 """KernelComputeForces::visit (main.cpp:12273-12493) restated in plain Python, line by line.  TEST INFRASTRUCTURE.
 
-The yardstick of k_surface_forces (cup3d_amd/csrc/obstacles.hip) on inputs of the tests' choosing (every path of the functor:
+The yardstick of k_surface_forces (cup3d_amd/csrc/obstacles_forces.hip) on inputs of the tests' choosing (every path of the functor:
 tests/surface_forces_cases.py), written out once more from the reference's text and not from the kernel; the compiled reference runs the
 functor on its own fish, and this restatement equals it there bit for bit (tests/test_fish_fixtures.py, tests/golden/fish_one_*.npz):
 scalar float64 arithmetic (Python floats: IEEE doubles, no contraction) in the reference's association, `round` half away from zero,

@@ -1,4 +1,4 @@
-"""What the compiler made of k_collision_sums (csrc/obstacles.hip), read from the code objects of both built libraries (no GPU): nothing
+"""What the compiler made of k_collision_sums (csrc/obstacles_collisions.hip), read from the code objects of both built libraries (no GPU): nothing
 in scratch, no vector register spilled, no accumulation register, at most 64 vector registers (eight wavefronts per SIMD).  One wavefront
 per obstacle; LDS holds the padded rows of one z-plane's summands -- the 14 sums, imag and jmag are the 16 it cannot do without -- plus
 the momenta of the cells the two scanning lanes choose from."""

@@ -1,4 +1,4 @@
-"""What the compiler made of the three kernels of cup3d_create_obstacles (csrc/obstacles.hip) and of the copy kernel between them, read
+"""What the compiler made of the three kernels of cup3d_create_obstacles (csrc/obstacles_create.hip) and of the copy kernel between them, read
 from the code objects of both built libraries (no GPU): nothing in scratch, no vector register spilled, no accumulation register.
 k_characteristic holds sdfLab (8 000 B), the block's chi (4 096 B) and four padded rows of summands (2 080 B) in LDS; k_udef_momenta the
 13 x 65 summands of one z-plane (6 760 B).  Both run one wavefront per block: the sums are added in cell order by single lanes."""

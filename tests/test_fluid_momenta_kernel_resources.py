@@ -1,4 +1,4 @@
-"""What the compiler made of k_fluid_momenta, the kernel of cup3d_update_obstacles (csrc/obstacles.hip), read from the code objects of both
+"""What the compiler made of k_fluid_momenta, the kernel of cup3d_update_obstacles (csrc/obstacles_update.hip), read from the code objects of both
 built libraries (no GPU): nothing in scratch, no vector register spilled, no accumulation register, and at most 16 KB of LDS per
 workgroup (the 29 x 64 summands of one z-plane of cells take 14 848 B; the rows are padded by one double against bank conflicts)."""
 import os

@@ -1,5 +1,5 @@
 """cup3d_create_obstacles: the grid half of CreateObstacles::operator() (main.cpp:13596-13619) -- k_characteristic, k_udef_momenta and
-k_remove_udef_momenta on the device, kernelComputeGridCoM and kernelAccumulateUdefMomenta on the host (csrc/obstacles.hip) -- against its
+k_remove_udef_momenta on the device, kernelComputeGridCoM and kernelAccumulateUdefMomenta on the host (csrc/obstacles_create.hip) -- against its
 plain-Python restatement (tests/characteristic_restatement.py, pinned by tests/test_characteristic_restatement.py) on the inputs of
 tests/characteristic_cases.py.  MI355X only (-m gpu).
 

@@ -165,7 +165,7 @@ def test_penalization(implicit, resident):
     same(got[ids], d[f"{tag}.vel"], "the obstacle's blocks of vel")
     rest = np.setdiff1d(np.arange(len(got)), ids)
     same(got[rest], d["vel"][rest], "every other block")
-    # force and torque are sums over all cells of the obstacle.  Not reproducible bitwise BY CONTRACT (csrc/obstacles.hip, header): the device
+    # force and torque are sums over all cells of the obstacle.  Not reproducible bitwise BY CONTRACT (csrc/obstacles.hpp, header): the device
     # adds a block's cells in tree order, the reference in iz, iy, ix order (13876-13909).  Two orders of one sum of N terms differ by at most
     # (N - 1) eps sum|term| each way.  Measured on MI355X (explicit, staged): max |d| = 1.4e-20 on force z = -3.65e-14, the sum of 348 terms
     # whose absolute values add up to 5.5e-6 (bound 8.4e-19); force x and y, which do not cancel, come out bit-equal.

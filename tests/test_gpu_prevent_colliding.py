@@ -1,5 +1,5 @@
 """cup3d_prevent_colliding_obstacles: Penalization::preventCollidingObstacles (main.cpp:14009-14324) -- k_collision_sums on the blocks
-cup3d_create_obstacles keeps on the device, the all-reduces and the pair loop on the host (csrc/obstacles.hip) -- against its plain-Python
+cup3d_create_obstacles keeps on the device, the all-reduces and the pair loop on the host (csrc/obstacles_collisions.hip) -- against its plain-Python
 restatement (tests/collision_restatement.py, pinned by tests/test_collision_restatement.py) on the scenarios of tests/collision_cases.py.
 MI355X only (-m gpu).
 

@@ -1,5 +1,5 @@
 """cup3d_update_obstacles_resident, cup3d_penalization_resident and cup3d_update_tmpv_resident -- UpdateObstacles, Penalization and
-kernelUpdateTmpV on the blocks cup3d_create_obstacles keeps on the device, one launch per operator (csrc/obstacles.hip) -- against the
+kernelUpdateTmpV on the blocks cup3d_create_obstacles keeps on the device, one launch per operator (csrc/obstacles_update.hip, csrc/obstacles_penalization.hip) -- against the
 staged entry points cup3d_update_obstacles, cup3d_penalization and cup3d_update_tmpv, which take the same chi and udef from the host,
 obstacle after obstacle.  MI355X only (-m gpu).
 

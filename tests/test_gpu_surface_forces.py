@@ -1,4 +1,4 @@
-"""cup3d_compute_forces: KernelComputeForces::visit (main.cpp:12273-12493) on the device (k_surface_forces, csrc/obstacles.hip) against its
+"""cup3d_compute_forces: KernelComputeForces::visit (main.cpp:12273-12493) on the device (k_surface_forces, csrc/obstacles_forces.hip) against its
 plain-Python restatement (tests/surface_forces_restatement.py) evaluated on the CPU oracle's [-4,5) tiles.  The inputs are those of
 tests/surface_forces_cases.py, which tests/test_surface_forces_cases.py shows to take every path of the functor.  MI355X only (-m gpu).
 

@@ -1,5 +1,5 @@
 """cup3d_update_obstacles: UpdateObstacles::operator() (main.cpp:13812-13837) -- k_fluid_momenta on the device, the block sum, the two
-penal* branches and Obstacle::computeVelocities on the host (csrc/obstacles.hip) -- against its plain-Python restatement
+penal* branches and Obstacle::computeVelocities on the host (csrc/obstacles_update.hip) -- against its plain-Python restatement
 (tests/fluid_momenta_restatement.py, pinned by tests/test_fluid_momenta_restatement.py) on the inputs of tests/fluid_momenta_cases.py.
 MI355X only (-m gpu).
 

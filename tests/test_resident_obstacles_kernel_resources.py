@@ -1,4 +1,4 @@
-"""What the compiler made of k_fluid_momenta_set, k_penalize_set and k_update_tmpv_set (csrc/obstacles.hip), read from the code objects
+"""What the compiler made of k_fluid_momenta_set, k_penalize_set and k_update_tmpv_set (csrc/obstacles_update.hip, csrc/obstacles_penalization.hip), read from the code objects
 of both built libraries (no GPU): nothing in scratch, no vector register spilled, no accumulation register.  k_fluid_momenta_set is
 k_fluid_momenta's body on one wavefront per row of the plan, with its padded LDS rows [29][65]; the other two run one 256-thread workgroup
 per touched slot."""

@@ -1,4 +1,4 @@
-"""What the compiler made of k_surface_forces, the kernel of cup3d_compute_forces (csrc/obstacles.hip), read from the code objects of both
+"""What the compiler made of k_surface_forces, the kernel of cup3d_compute_forces (csrc/obstacles_forces.hip), read from the code objects of both
 built libraries (no GPU): nothing in scratch, no vector register spilled, no accumulation register, and at most 16 KB of LDS per
 workgroup (the 19 x 64 summands of one chunk of points take 9 728 B)."""
 import os

@@ -149,13 +149,6 @@ static int child_table(const Sim *coarse, const Sim *fine, std::vector<int32_t> 
   return CUP3D_OK;
 }
 
-template <typename T>
-static int upload(std::vector<T> &h, T **d) {
-  CUP3D_HIP(hipMalloc((void **)d, h.size() * sizeof(T)));
-  CUP3D_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return CUP3D_OK;
-}
-
 }  // namespace cup3d
 
 using namespace cup3d;
@@ -171,15 +164,14 @@ int cup3d_restrict(cup3d_sim_t *fine_h, cup3d_sim_t *coarse_h, int field) {
   const double *src = fine->field(field, &nc);
   double *dst = coarse->field(field, &nc2);
   if (!src || !dst) { set_error("unknown field id %d", field); return CUP3D_EINVAL; }
-  int32_t *d_tab;
-  if ((rc = upload(tab, &d_tab))) return rc;
+  Dev<int32_t> d_tab;
+  if ((rc = d_tab.upload(tab, IfEmpty::null))) return rc;
   {
     ProfileScope ps("restrict_blocks");
-    hipLaunchKernelGGL(k_restrict, dim3((unsigned)coarse->nb), dim3(256), 0, stream(), src, dst, d_tab, nc);
+    hipLaunchKernelGGL(k_restrict, dim3((unsigned)coarse->nb), dim3(256), 0, stream(), src, dst, d_tab.get(), nc);
   }
   CUP3D_HIP(hipGetLastError());
-  CUP3D_HIP(hipStreamSynchronize(stream()));
-  CUP3D_HIP(hipFree(d_tab));
+  CUP3D_HIP(hipStreamSynchronize(stream()));  // the table is freed on return
   return CUP3D_OK;
 }
 
@@ -195,17 +187,15 @@ int cup3d_prolong(cup3d_sim_t *coarse_h, cup3d_sim_t *fine_h, int field) {
   std::vector<int32_t> n27 = coarse->grid->neighbours27();
   for (int32_t v : n27)
     if (v == -2) { set_error("cup3d_prolong: a neighbour block lives on another rank (multi-rank mesh adaptation is not wired yet)"); return CUP3D_ESTATE; }
-  int32_t *d_tab, *d_n27;
-  if ((rc = upload(tab, &d_tab)) || (rc = upload(n27, &d_n27))) return rc;
+  Dev<int32_t> d_tab, d_n27;
+  if ((rc = d_tab.upload(tab, IfEmpty::null)) || (rc = d_n27.upload(n27, IfEmpty::null))) return rc;
   {
     ProfileScope ps("prolong_blocks");
-    if (nc == 3) hipLaunchKernelGGL(k_prolong<3>, dim3((unsigned)coarse->nb), dim3(256), 0, stream(), src, dst, d_n27, coarse->d_nbr, d_tab);
-    else hipLaunchKernelGGL(k_prolong<1>, dim3((unsigned)coarse->nb), dim3(256), 0, stream(), src, dst, d_n27, coarse->d_nbr, d_tab);
+    if (nc == 3) hipLaunchKernelGGL(k_prolong<3>, dim3((unsigned)coarse->nb), dim3(256), 0, stream(), src, dst, d_n27.get(), coarse->d_nbr.get(), d_tab.get());
+    else hipLaunchKernelGGL(k_prolong<1>, dim3((unsigned)coarse->nb), dim3(256), 0, stream(), src, dst, d_n27.get(), coarse->d_nbr.get(), d_tab.get());
   }
   CUP3D_HIP(hipGetLastError());
-  CUP3D_HIP(hipStreamSynchronize(stream()));
-  CUP3D_HIP(hipFree(d_tab));
-  CUP3D_HIP(hipFree(d_n27));
+  CUP3D_HIP(hipStreamSynchronize(stream()));  // the tables are freed on return
   return CUP3D_OK;
 }
 
@@ -216,18 +206,18 @@ int cup3d_tag_blocks(cup3d_sim_t *h, int field, double rtol, double ctol, signed
   const double *f = s->field(field, &nc);
   if (!f) { set_error("unknown field id %d", field); return CUP3D_EINVAL; }
   const Grid *gr = s->grid;
-  signed char *d_states;
-  CUP3D_HIP(hipMalloc((void **)&d_states, (size_t)s->nb));
+  Dev<signed char> d_states;
+  int rc = d_states.alloc((size_t)s->nb);
+  if (rc) return rc;
   {
     ProfileScope ps("tag_blocks");
     // multi-level meshes: the level clamps differ per block and are applied on the host below
     hipLaunchKernelGGL(k_tag, dim3((unsigned)s->nb), dim3(256), 0, stream(), f, nc, rtol, ctol,
-                       (!gr->multilevel && gr->level == gr->level_max - 1) ? 1 : 0, (!gr->multilevel && gr->level == 0) ? 1 : 0, d_states);
+                       (!gr->multilevel && gr->level == gr->level_max - 1) ? 1 : 0, (!gr->multilevel && gr->level == 0) ? 1 : 0, d_states.get());
   }
   CUP3D_HIP(hipGetLastError());
   CUP3D_HIP(hipMemcpyAsync(states, d_states, (size_t)s->nb, hipMemcpyDeviceToHost, stream()));
   CUP3D_HIP(hipStreamSynchronize(stream()));
-  CUP3D_HIP(hipFree(d_states));
   if (gr->multilevel)
     for (int64_t b = 0; b < s->nb; ++b) {  // TagBlocksVector, main.cpp:5207-5211
       if (states[b] == 1 && gr->blevel[b] == gr->level_max - 1) states[b] = 0;

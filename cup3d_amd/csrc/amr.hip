@@ -536,24 +536,6 @@ int amr_flux_fix(Sim *s, int nfc, double *out, int out_nc) {
 using namespace cup3d;
 
 namespace {
-struct DevInts {
-  int32_t *p = nullptr;
-  int upload(const std::vector<int32_t> &v) {
-    if (v.empty()) return CUP3D_OK;
-    CUP3D_HIP(hipMalloc((void **)&p, v.size() * sizeof(int32_t)));
-    CUP3D_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream()));
-    return CUP3D_OK;
-  }
-  ~DevInts() { if (p) hipFree(p); }
-};
-struct DevBuf {
-  void *p = nullptr;
-  int alloc(size_t bytes) {
-    CUP3D_HIP(hipMalloc(&p, bytes));
-    return CUP3D_OK;
-  }
-  ~DevBuf() { if (p) hipFree(p); }
-};
 __global__ void __launch_bounds__(256) k_pack_blocks(const double *__restrict__ field, const int32_t *__restrict__ slots, int nc, double *__restrict__ out) {
   const double *src = field + (size_t)slots[blockIdx.x] * nc * 512;
   double *dst = out + (size_t)blockIdx.x * nc * 512;
@@ -601,11 +583,9 @@ static void finer_tables(const Grid *mo, int64_t nloc, std::vector<int32_t> &fin
 // rank, a rank's tensorial view over ranks).  One owner for the four users: cup3d_sim_labs and cup3d_sim_labs_over_ranks keep theirs in
 // the sim, mesh adaptation and GradChiOnTmp build one per call and let it go after their stream synchronise.
 struct LabIndex {
-  int32_t *n27 = nullptr, *index = nullptr, *level = nullptr, *finer_row = nullptr, *finer = nullptr;
+  Dev<int32_t> n27, index, level, finer_row, finer;
   std::vector<int32_t> h_finer_row, h_finer;  // the two tables `mo` does not hold, on the host
   size_t bytes = 0;                           // of the five tables
-  LabIndex() = default;
-  LabIndex(const LabIndex &) = delete;
   int build(const Grid *mo, int64_t nloc, const char *who) {
     try {
       finer_tables(mo, nloc, h_finer_row, h_finer);
@@ -613,10 +593,10 @@ struct LabIndex {
       set_error("%s: %s", who, e.what());
       return CUP3D_EINVAL;
     }
-    const std::pair<int32_t **, const std::vector<int32_t> *> tables[] = {{&n27, &mo->nbr27}, {&index, &mo->index}, {&level, &mo->blevel}, {&finer_row, &h_finer_row}, {&finer, &h_finer}};
+    const std::pair<Dev<int32_t> *, const std::vector<int32_t> *> tables[] = {{&n27, &mo->nbr27}, {&index, &mo->index}, {&level, &mo->blevel}, {&finer_row, &h_finer_row}, {&finer, &h_finer}};
     for (const auto &[d, v] : tables) {
-      CUP3D_HIP(hipMalloc((void **)d, std::max<size_t>(v->size(), 1) * sizeof(int32_t)));
-      if (!v->empty()) CUP3D_HIP(hipMemcpy(*d, v->data(), v->size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      int rc = d->upload(*v, IfEmpty::one);
+      if (rc) return rc;
       bytes += v->size() * sizeof(int32_t);
     }
     return CUP3D_OK;
@@ -624,10 +604,6 @@ struct LabIndex {
   // box and boundary conditions come from `g`: the sim's grid, or the mesh object itself
   LabDev dev(const Grid *g, int bc_comp) const {
     return LabDev{n27, index, level, finer_row, finer, {g->bpd[0], g->bpd[1], g->bpd[2]}, {g->bc[0], g->bc[1], g->bc[2]}, bc_comp};
-  }
-  ~LabIndex() {
-    for (void *p : {(void *)n27, (void *)index, (void *)level, (void *)finer_row, (void *)finer})
-      if (p) (void)hipFree(p);
   }
 };
 
@@ -674,7 +650,7 @@ static int adapt_produce(const Grid *mo, const std::vector<NewBlock> &blocks, co
     return CUP3D_EINVAL;
   }
   LabIndex tab;
-  DevInts d_pairs, d_octets, d_items;
+  Dev<int32_t> d_pairs, d_octets, d_items;
   int rc;
   if (!items.empty()) {
     if ((rc = tab.build(mo, mo->nblocks(), "mesh adaptation"))) return rc;
@@ -692,15 +668,15 @@ static int adapt_produce(const Grid *mo, const std::vector<NewBlock> &blocks, co
       }
     }
   }
-  if ((rc = d_pairs.upload(pairs)) || (rc = d_octets.upload(octets)) || (rc = d_items.upload(items))) return rc;
+  if ((rc = d_pairs.upload(pairs, stream(), IfEmpty::null)) || (rc = d_octets.upload(octets, stream(), IfEmpty::null)) || (rc = d_items.upload(items, stream(), IfEmpty::null))) return rc;
   ProfileScope ps("adapt_transfer");
-  if (!pairs.empty()) hipLaunchKernelGGL(k_copy_blocks, dim3((unsigned)(pairs.size() / 2)), dim3(256), 0, stream(), d_pairs.p, fs, fd, nc);
-  if (!octets.empty()) hipLaunchKernelGGL(k_compress_blocks, dim3((unsigned)(octets.size() / 9)), dim3(256), 0, stream(), d_octets.p, fs, fd, nc);
+  if (!pairs.empty()) hipLaunchKernelGGL(k_copy_blocks, dim3((unsigned)(pairs.size() / 2)), dim3(256), 0, stream(), d_pairs.get(), fs, fd, nc);
+  if (!octets.empty()) hipLaunchKernelGGL(k_compress_blocks, dim3((unsigned)(octets.size() / 9)), dim3(256), 0, stream(), d_octets.get(), fs, fd, nc);
   if (!items.empty()) {
     const LabDev a = tab.dev(mo, -1);
     const unsigned n = (unsigned)(items.size() / 9);
-    if (nc == 3) hipLaunchKernelGGL(k_refine<3>, dim3(n), dim3(256), 0, stream(), a, (const int32_t *)d_items.p, fs, fd);
-    else hipLaunchKernelGGL(k_refine<1>, dim3(n), dim3(256), 0, stream(), a, (const int32_t *)d_items.p, fs, fd);
+    if (nc == 3) hipLaunchKernelGGL(k_refine<3>, dim3(n), dim3(256), 0, stream(), a, (const int32_t *)d_items, fs, fd);
+    else hipLaunchKernelGGL(k_refine<1>, dim3(n), dim3(256), 0, stream(), a, (const int32_t *)d_items, fs, fd);
   }
   CUP3D_HIP(hipGetLastError());
   CUP3D_HIP(hipStreamSynchronize(stream()));  // the index tables above are freed on return
@@ -754,8 +730,8 @@ extern "C" int cup3d_adapt_migrate(const cup3d_grid_t *old_mesh_h, const int32_t
   std::vector<int64_t> send_count(nranks, 0), recv_count(nranks, 0);
   std::vector<int32_t> recv_slots;          // local slots of dst in arrival order: by (producer, new global slot)
   size_t per = 0;
-  DevBuf F, prod, recv, pack;
-  DevInts d_send, d_recv_slots;
+  Dev<double> F, prod, recv, pack;
+  Dev<int32_t> d_send, d_recv_slots;
   // everything this rank can get wrong on its own -- arguments, the plan, allocations -- happens in here; the ranks then agree on the
   // outcome BEFORE the first exchange, so that a bad call on one rank returns an error on every rank instead of blocking the others
   auto local_part = [&]() -> int {
@@ -797,27 +773,26 @@ extern "C" int cup3d_adapt_migrate(const cup3d_grid_t *old_mesh_h, const int32_t
     per = (size_t)nc * 512;
     const size_t nvis = tv->Z.size();
     int rc;
-    if ((rc = F.alloc(nvis * per * sizeof(double))) || (rc = prod.alloc(std::max<size_t>(mine.size(), 1) * per * sizeof(double))) ||
-        (rc = recv.alloc(std::max<size_t>(recv_slots.size(), 1) * per * sizeof(double))) ||
-        (rc = pack.alloc(std::max<size_t>(tv->send_blocks.size(), 1) * per * sizeof(double))) || (rc = d_send.upload(tv->send_blocks)))
+    if ((rc = F.alloc(nvis * per)) || (rc = prod.alloc(std::max<size_t>(mine.size(), 1) * per)) || (rc = recv.alloc(std::max<size_t>(recv_slots.size(), 1) * per)) ||
+        (rc = pack.alloc(std::max<size_t>(tv->send_blocks.size(), 1) * per)) || (rc = d_send.upload(tv->send_blocks, stream(), IfEmpty::null)))
       return rc;
     // the old field on the tensorial view: local blocks (the ghost blocks arrive from their owners below)
-    CUP3D_HIP(hipMemcpyAsync(F.p, fs, (size_t)src->nb * per * sizeof(double), hipMemcpyDeviceToDevice, stream()));
+    CUP3D_HIP(hipMemcpyAsync(F, fs, (size_t)src->nb * per * sizeof(double), hipMemcpyDeviceToDevice, stream()));
     if (!tv->send_blocks.empty())
-      hipLaunchKernelGGL(k_pack_blocks, dim3((unsigned)tv->send_blocks.size()), dim3(256), 0, stream(), (const double *)F.p, d_send.p, nc, (double *)pack.p);
+      hipLaunchKernelGGL(k_pack_blocks, dim3((unsigned)tv->send_blocks.size()), dim3(256), 0, stream(), (const double *)F, d_send.get(), nc, pack.get());
     CUP3D_HIP(hipGetLastError());
     return CUP3D_OK;
   };
   int rc = agree(src, local_part(), "cup3d_adapt_migrate");
   if (rc) return rc;
-  if ((rc = exchange_items(src, (const double *)pack.p, tv->send_block_count, (double *)F.p + (size_t)tv->n_local * per, tv->recv_block_count, per))) return rc;
+  if ((rc = exchange_items(src, pack, tv->send_block_count, F + (size_t)tv->n_local * per, tv->recv_block_count, per))) return rc;
   CUP3D_HIP(hipStreamSynchronize(stream()));
   // producing the new blocks is rank-local again (kernels, table uploads): agree once more before they travel
-  if ((rc = agree(src, adapt_produce(tv.get(), mine, (const double *)F.p, (double *)prod.p, nc), "cup3d_adapt_migrate (produce)"))) return rc;
-  if ((rc = exchange_items(src, (const double *)prod.p, send_count, (double *)recv.p, recv_count, per))) return rc;
+  if ((rc = agree(src, adapt_produce(tv.get(), mine, F, prod, nc), "cup3d_adapt_migrate (produce)"))) return rc;
+  if ((rc = exchange_items(src, prod, send_count, recv, recv_count, per))) return rc;
   if (!recv_slots.empty()) {
-    if ((rc = d_recv_slots.upload(recv_slots))) return rc;
-    hipLaunchKernelGGL(k_unpack_blocks, dim3((unsigned)recv_slots.size()), dim3(256), 0, stream(), (const double *)recv.p, d_recv_slots.p, nc, fd);
+    if ((rc = d_recv_slots.upload(recv_slots, stream(), IfEmpty::null))) return rc;
+    hipLaunchKernelGGL(k_unpack_blocks, dim3((unsigned)recv_slots.size()), dim3(256), 0, stream(), (const double *)recv, d_recv_slots.get(), nc, fd);
     CUP3D_HIP(hipGetLastError());
   }
   CUP3D_HIP(hipStreamSynchronize(stream()));
@@ -865,8 +840,8 @@ extern "C" int cup3d_grad_chi_on_tmp_over_ranks(cup3d_sim_t *h, const cup3d_grid
   const Grid *gm = reinterpret_cast<const Grid *>(mesh_h);
   const int me = s->grid->rank, nranks = s->grid->nranks;
   std::unique_ptr<Grid> tv;
-  DevBuf F, pack;
-  DevInts d_send;
+  Dev<double> F, pack;
+  Dev<int32_t> d_send;
   auto local_part = [&]() -> int {  // what one rank can get wrong on its own; the ranks agree on the outcome before anything is exchanged
     if (!mesh_h || !owner) { set_error("cup3d_grad_chi_on_tmp_over_ranks: null argument"); return CUP3D_EINVAL; }
     if (!gm->multilevel || gm->n_local >= 0) { set_error("cup3d_grad_chi_on_tmp_over_ranks needs the GLOBAL mesh object"); return CUP3D_EINVAL; }
@@ -879,20 +854,18 @@ extern "C" int cup3d_grad_chi_on_tmp_over_ranks(cup3d_sim_t *h, const cup3d_grid
     }
     const size_t nvis = tv->Z.size();
     int rc;
-    if ((rc = F.alloc(nvis * 512 * sizeof(double))) || (rc = pack.alloc(std::max<size_t>(tv->send_blocks.size(), 1) * 512 * sizeof(double))) ||
-        (rc = d_send.upload(tv->send_blocks)))
-      return rc;
-    CUP3D_HIP(hipMemcpyAsync(F.p, s->chi, (size_t)s->nb * 512 * sizeof(double), hipMemcpyDeviceToDevice, stream()));
+    if ((rc = F.alloc(nvis * 512)) || (rc = pack.alloc(std::max<size_t>(tv->send_blocks.size(), 1) * 512)) || (rc = d_send.upload(tv->send_blocks, stream(), IfEmpty::null))) return rc;
+    CUP3D_HIP(hipMemcpyAsync(F, s->chi, (size_t)s->nb * 512 * sizeof(double), hipMemcpyDeviceToDevice, stream()));
     if (!tv->send_blocks.empty())
-      hipLaunchKernelGGL(k_pack_blocks, dim3((unsigned)tv->send_blocks.size()), dim3(256), 0, stream(), (const double *)F.p, d_send.p, 1, (double *)pack.p);
+      hipLaunchKernelGGL(k_pack_blocks, dim3((unsigned)tv->send_blocks.size()), dim3(256), 0, stream(), (const double *)F, d_send.get(), 1, pack.get());
     CUP3D_HIP(hipGetLastError());
     return CUP3D_OK;
   };
   int rc = agree(s, local_part(), "cup3d_grad_chi_on_tmp_over_ranks");
   if (rc) return rc;
-  if ((rc = exchange_items(s, (const double *)pack.p, tv->send_block_count, (double *)F.p + (size_t)tv->n_local * 512, tv->recv_block_count, 512))) return rc;
+  if ((rc = exchange_items(s, pack, tv->send_block_count, F + (size_t)tv->n_local * 512, tv->recv_block_count, 512))) return rc;
   CUP3D_HIP(hipStreamSynchronize(stream()));
-  return grad_chi_run(tv.get(), tv->n_local, (const double *)F.p, s->tmpV, Rtol, Ctol, level_max_vorticity);
+  return grad_chi_run(tv.get(), tv->n_local, F, s->tmpV, Rtol, Ctol, level_max_vorticity);
 }
 
 // TEST SUPPORT: the ghost slabs of every interface face for `field` and a w-deep stencil, [(e*nc + c)*w + gl][64]
@@ -921,22 +894,18 @@ constexpr long kLabSlotCap = 8192;                   // listed tiles per launch 
 
 struct LabTables {
   LabIndex tab;
-  int32_t *d_slots = nullptr, *h_slots = nullptr;  // slot list of one launch: device copy, pinned host copy
+  Dev<int32_t> d_slots;     // slot list of one launch: device copy,
+  Pinned<int32_t> h_slots;  // pinned host copy
   hipEvent_t ev_slots = nullptr;                   // the upload that last read h_slots
   bool slots_in_flight = false;
-  double *stage = nullptr;
+  Dev<double> stage;
+  ~LabTables() { if (ev_slots) (void)hipEventDestroy(ev_slots); }
 };
 
 static void labs_view_destroy(Sim *s);
 void labs_destroy(Sim *s) {
   labs_view_destroy(s);  // the cached view, its tables and the ghost pool of cup3d_sim_labs_over_ranks
-  LabTables *T = s->labs;
-  if (!T) return;
-  if (T->d_slots) (void)hipFree(T->d_slots);
-  if (T->stage) (void)hipFree(T->stage);
-  if (T->h_slots) (void)hipHostFree(T->h_slots);
-  if (T->ev_slots) (void)hipEventDestroy(T->ev_slots);
-  delete T;
+  delete s->labs;
   s->labs = nullptr;
 }
 
@@ -953,25 +922,24 @@ static int labs_prepare(Sim *s, bool want_stage) {
     }
     s->labs = new LabTables();
     LabTables *T = s->labs;
-    int rc = T->tab.build(mo, mo->nblocks(), "cup3d_sim_labs");
-    if (rc) {
-      labs_destroy(s);
+    auto build = [&]() -> int {
+      int rc = T->tab.build(mo, mo->nblocks(), "cup3d_sim_labs");
+      if (rc) return rc;
+      s->bytes += T->tab.bytes;
+      if ((rc = T->d_slots.alloc(kLabSlotCap, s)) || (rc = T->h_slots.alloc(kLabSlotCap, hipHostMallocDefault))) return rc;
+      CUP3D_HIP(hipEventCreateWithFlags(&T->ev_slots, hipEventDisableTiming));
+      return CUP3D_OK;
+    };
+    const size_t before = s->bytes;
+    const int rc = build();
+    if (rc) {  // all or nothing, on the ledger too
+      delete s->labs;
+      s->labs = nullptr;
+      s->bytes = before;
       return rc;
     }
-    s->bytes += T->tab.bytes;
-    hipError_t e = hipMalloc((void **)&T->d_slots, kLabSlotCap * sizeof(int32_t));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&T->h_slots, kLabSlotCap * sizeof(int32_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&T->ev_slots, hipEventDisableTiming);
-    if (e != hipSuccess) {
-      labs_destroy(s);
-      return hip_fail(e, "labs_prepare", __FILE__, __LINE__);
-    }
-    s->bytes += kLabSlotCap * sizeof(int32_t);
   }
-  if (want_stage && !s->labs->stage) {
-    CUP3D_HIP(hipMalloc((void **)&s->labs->stage, kLabStageBytes));
-    s->bytes += kLabStageBytes;
-  }
+  if (want_stage && !s->labs->stage) return s->labs->stage.alloc(kLabStageBytes / sizeof(double), s);
   return CUP3D_OK;
 }
 
@@ -1067,20 +1035,6 @@ extern "C" int cup3d_sim_labs(cup3d_sim_t *h, int field, long n, const int32_t *
 // Everything crosses ranks through agree() and exchange_items() (RCCL, the host transport, the in-process test communicator).
 namespace cup3d {
 
-struct DevGrow {  // a device buffer that only grows
-  void *p = nullptr;
-  size_t cap = 0;
-  int need(size_t bytes, Sim *s) {
-    if (bytes <= cap) return CUP3D_OK;
-    if (p) { (void)hipFree(p); s->bytes -= cap; p = nullptr; cap = 0; }
-    CUP3D_HIP(hipMalloc(&p, bytes));
-    cap = bytes;
-    s->bytes += bytes;
-    return CUP3D_OK;
-  }
-  void release(Sim *s) { if (p) { (void)hipFree(p); s->bytes -= cap; } p = nullptr; cap = 0; }
-};
-
 struct LabsView {
   // the cache key is CONTENT: the leaves of the mesh and the owner of each (a pointer can be freed and reused)
   std::vector<int32_t> key_level, key_owner;
@@ -1100,10 +1054,8 @@ struct LabsView {
 static void labs_view_destroy(Sim *s) {
   LabsView *V = s->labs_view;
   if (!V) return;
-  DevGrow *g[] = {&V->d_req, &V->d_got, &V->d_pool_of, &V->d_sslots, &V->d_sbox, &V->d_soff, &V->d_rbox, &V->d_roff, &V->d_pack, &V->d_recv, &V->d_pool, &V->d_slots, &V->d_stage};
-  for (DevGrow *b : g) b->release(s);
   s->bytes -= V->tab.bytes;
-  delete V;
+  delete V;  // the grow-only buffers take their own bytes off
   s->labs_view = nullptr;
 }
 
@@ -1164,14 +1116,6 @@ static bool box_decode(double v, uint8_t *b, int64_t *vol) {
   return true;
 }
 
-template <class T>
-static int upload_vec(DevGrow &d, const std::vector<T> &v, Sim *s) {
-  int rc = d.need(std::max<size_t>(v.size(), 1) * sizeof(T), s);
-  if (rc) return rc;
-  if (!v.empty()) CUP3D_HIP(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream()));
-  return CUP3D_OK;
-}
-
 static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int32_t *owner, int field, long n, const int32_t *slots, int width, int tensorial,
                            int scalar_dir, void *out, bool to_host) {
   if (!h) return CUP3D_EINVAL;  // (without the sim there is no communicator to tell the other ranks through)
@@ -1198,10 +1142,10 @@ static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int
     V->h_req.resize(ng);
     for (size_t g = 0; g < ng; ++g) V->h_req[g] = box_encode(V->gbox.data() + 6 * g);
     V->h_got.assign(tv->send_blocks.size(), 0.0);
-    if ((rc = upload_vec(V->d_req, V->h_req, s)) || (rc = V->d_got.need(std::max<size_t>(V->h_got.size(), 1) * sizeof(double), s))) return rc;
+    if ((rc = V->d_req.upload(V->h_req, stream(), s)) || (rc = V->d_got.need(std::max<size_t>(V->h_got.size(), 1) * sizeof(double), s))) return rc;
     if (n && slots) {
       V->tile_slots.assign(slots, slots + n);
-      if ((rc = upload_vec(V->d_slots, V->tile_slots, s))) return rc;
+      if ((rc = V->d_slots.upload(V->tile_slots, stream(), s))) return rc;
     }
     return CUP3D_OK;
   };
@@ -1213,8 +1157,8 @@ static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int
   // ---- request: my ghosts' boxes -> their owners; what comes back is what I have to pack
   {
     ProfileScope ps("labs_request");
-    if ((rc = exchange_items(s, (const double *)V->d_req.p, tv->recv_block_count, (double *)V->d_got.p, tv->send_block_count, 1))) return rc;
-    if (nsend) CUP3D_HIP(hipMemcpyAsync(V->h_got.data(), V->d_got.p, nsend * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    if ((rc = exchange_items(s, V->d_req.as<const double>(), tv->recv_block_count, V->d_got.as<double>(), tv->send_block_count, 1))) return rc;
+    if (nsend) CUP3D_HIP(hipMemcpyAsync(V->h_got.data(), V->d_got.get(), nsend * sizeof(double), hipMemcpyDeviceToHost, stream()));
     CUP3D_HIP(hipStreamSynchronize(stream()));
   }
   // ---- the two sides of the data exchange
@@ -1254,20 +1198,20 @@ static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int
   const size_t pool_doubles = ((size_t)nrows + 1) * per;
   {
     ProfileScope ps("labs_data");
-    if ((rc = upload_vec(V->d_sslots, pslots, s)) || (rc = upload_vec(V->d_sbox, V->sbox, s)) || (rc = upload_vec(V->d_soff, V->soff, s)) ||
-        (rc = upload_vec(V->d_rbox, V->rbox, s)) || (rc = upload_vec(V->d_roff, V->roff, s)) || (rc = upload_vec(V->d_pool_of, V->pool_of, s)) ||
+    if ((rc = V->d_sslots.upload(pslots, stream(), s)) || (rc = V->d_sbox.upload(V->sbox, stream(), s)) || (rc = V->d_soff.upload(V->soff, stream(), s)) ||
+        (rc = V->d_rbox.upload(V->rbox, stream(), s)) || (rc = V->d_roff.upload(V->roff, stream(), s)) || (rc = V->d_pool_of.upload(V->pool_of, stream(), s)) ||
         (rc = V->d_pack.need(std::max<size_t>((size_t)so * nc, 1) * sizeof(double), s)) || (rc = V->d_recv.need(std::max<size_t>((size_t)ro * nc, 1) * sizeof(double), s)) ||
         (rc = V->d_pool.need(pool_doubles * sizeof(double), s)))
       return rc;
     CUP3D_HIP(hipStreamSynchronize(stream()));  // pslots is a local: its upload has read it
-    if ((rc = launch_pack_boxes(f, (const int32_t *)V->d_sslots.p, (const unsigned char *)V->d_sbox.p, (const long long *)V->d_soff.p, nc, (double *)V->d_pack.p,
+    if ((rc = launch_pack_boxes(f, V->d_sslots.as<const int32_t>(), V->d_sbox.as<const unsigned char>(), V->d_soff.as<const long long>(), nc, V->d_pack.as<double>(),
                                 (unsigned)pslots.size(), stream())))
       return rc;
-    if ((rc = exchange_items(s, (const double *)V->d_pack.p, V->send_cells, (double *)V->d_recv.p, V->recv_cells, (size_t)nc))) return rc;
+    if ((rc = exchange_items(s, V->d_pack.as<const double>(), V->send_cells, V->d_recv.as<double>(), V->recv_cells, (size_t)nc))) return rc;
     // row 0 of the pool is what a ghost block that was not fetched reads as: NaN.  "poison_ghosts" (tests): so does every cell of a
     // fetched block that did not travel, as after the star exchange
-    if ((rc = launch_nan_fill((double *)V->d_pool.p, debug_option("poison_ghosts") ? pool_doubles : per, stream()))) return rc;
-    if ((rc = launch_unpack_boxes((double *)V->d_pool.p + per, (const unsigned char *)V->d_rbox.p, (const long long *)V->d_roff.p, nc, (const double *)V->d_recv.p,
+    if ((rc = launch_nan_fill(V->d_pool.as<double>(), debug_option("poison_ghosts") ? pool_doubles : per, stream()))) return rc;
+    if ((rc = launch_unpack_boxes(V->d_pool.as<double>() + per, V->d_rbox.as<const unsigned char>(), V->d_roff.as<const long long>(), nc, V->d_recv.as<const double>(),
                                   (unsigned)nrows, stream())))
       return rc;
   }
@@ -1277,7 +1221,7 @@ static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int
     return CUP3D_OK;
   }
   const LabDev a = V->tab.dev(s->grid, nc == 1 ? scalar_dir : -1);
-  LabSrcView src{f, (const double *)V->d_pool.p, (const int32_t *)V->d_pool_of.p, (int)tv->n_local};
+  LabSrcView src{f, V->d_pool.as<const double>(), V->d_pool_of.as<const int32_t>(), (int)tv->n_local};
   const int star = tensorial ? 0 : 1;
   const size_t L = 8 + 2 * (size_t)width, tile = L * L * L * nc;
   long cap = n;
@@ -1287,8 +1231,8 @@ static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int
   }
   for (long t0 = 0; t0 < n; t0 += cap) {  // the host variant goes through its bounded staging buffer chunk by chunk
     const long m = std::min(cap, n - t0);
-    double *dst = to_host ? (double *)V->d_stage.p : (double *)out + (size_t)t0 * tile;
-    const int32_t *sl = slots ? (const int32_t *)V->d_slots.p + t0 : nullptr;
+    double *dst = to_host ? V->d_stage.as<double>() : (double *)out + (size_t)t0 * tile;
+    const int32_t *sl = slots ? V->d_slots.as<const int32_t>() + t0 : nullptr;
     {
       ProfileScope ps("labs_view");
       switch (width) {
@@ -1300,7 +1244,7 @@ static int labs_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh_h, const int
     }
     CUP3D_HIP(hipGetLastError());
     if (to_host) {
-      CUP3D_HIP(hipMemcpyAsync((double *)out + (size_t)t0 * tile, V->d_stage.p, (size_t)m * tile * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipMemcpyAsync((double *)out + (size_t)t0 * tile, V->d_stage.get(), (size_t)m * tile * sizeof(double), hipMemcpyDeviceToHost, stream()));
       CUP3D_HIP(hipStreamSynchronize(stream()));
     }
   }

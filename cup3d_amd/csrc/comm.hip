@@ -125,7 +125,7 @@ struct VComm {
   std::vector<Sim *> cur;    // the sim each rank entered the CURRENT collective with (a rank can hold two: old and adapted mesh)
   std::vector<double *> ptr;
   std::vector<const std::vector<int64_t> *> counts;
-  double *d_tmp = nullptr;  // [n][16]
+  Dev<double> d_tmp;  // [n][16]
   std::vector<int> codes;   // agree(): the status every rank arrived with
   std::mutex m;
   std::condition_variable cv;
@@ -731,7 +731,6 @@ int cup3d_debug_virtual_ranks(int on) {
 int cup3d_debug_virtual_comm(int nranks) {
   if (nranks < 0 || nranks > 16) return CUP3D_EINVAL;
   if (g_vcomm) {
-    if (g_vcomm->d_tmp) hipFree(g_vcomm->d_tmp);
     delete g_vcomm;
     g_vcomm = nullptr;
     g_virtual_ranks = false;
@@ -744,7 +743,7 @@ int cup3d_debug_virtual_comm(int nranks) {
   vc->ptr.assign(nranks, nullptr);
   vc->counts.assign(nranks, nullptr);
   vc->codes.assign(nranks, 0);
-  if (hipMalloc((void **)&vc->d_tmp, (size_t)nranks * 16 * sizeof(double)) != hipSuccess) { delete vc; set_error("virtual communicator: hipMalloc failed"); return CUP3D_EDEVICE; }
+  if (vc->d_tmp.alloc((size_t)nranks * 16)) { delete vc; set_error("virtual communicator: hipMalloc failed"); return CUP3D_EDEVICE; }
   g_vcomm = vc;
   g_virtual_ranks = true;
   return CUP3D_OK;

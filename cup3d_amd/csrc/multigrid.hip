@@ -34,22 +34,24 @@ struct MGLevel {
   int index = 0;               // position in Multigrid::lev (0 = coarsest): the per-level entries of the profile
   int64_t nb = 0;
   double h = 0;
-  int32_t *d_nbr = nullptr;     // [nb][6]
-  int32_t *d_parent = nullptr;  // [nb][2]: slot of the parent block on the next coarser level, octant (x + 2y + 4z)
-  double *x = nullptr, *x2 = nullptr, *b = nullptr;  // coarse levels; the finest level uses the caller's vectors + x2
-  bool own_nbr = false;
+  // What a level borrows from the solver's Sim (the finest level of a uniform grid: its neighbour table, the Sim itself as `xch`) it
+  // holds as the plain pointer the kernels take, next to an owner that stays empty; what it made itself, in both.
+  const int32_t *d_nbr = nullptr;  // [nb][6]
+  Dev<int32_t> own_nbr;
+  Dev<int32_t> d_parent;  // [nb][2]: slot of the parent block on the next coarser level, octant (x + 2y + 4z)
+  Dev<double> x, x2, b;   // coarse levels; the finest level uses the caller's vectors + x2
   // multi-level meshes (mg_setup_amr): the nodes of octree level l = its leaves + the ancestors of finer leaves
-  int32_t *d_leaf = nullptr;    // [nb] slot of the leaf in the solver's mesh, -1 for an ancestor
-  int32_t *d_cf = nullptr;      // [ncf][4] faces without a same-level neighbour: coarse node slot (level l-1), direction, side, tangential parities
+  Dev<int32_t> d_leaf;    // [nb] slot of the leaf in the solver's mesh, -1 for an ancestor
+  Dev<int32_t> d_cf;      // [ncf][4] faces without a same-level neighbour: coarse node slot (level l-1), direction, side, tangential parities
   int64_t ncf = 0;
-  double *slabs = nullptr;      // [ncf][64] ghost values behind those faces, injected from the coarse iterate
+  Dev<double> slabs;      // [ncf][64] ghost values behind those faces, injected from the coarse iterate
   Sim *xch = nullptr;           // several ranks: what halo_exchange() needs for this level's iterate (the solver's Sim on the finest level)
-  bool own_xch = false;
+  std::unique_ptr<Sim, void (*)(Sim *)> own_xch{nullptr, sim_comm_only_destroy};
   // multi-level meshes over ranks (Grid::mg_hierarchy): the arrays hold nb owned nodes + nghost ghost nodes; the exchange plans
   const MGLevelPlan *plan = nullptr;
   int64_t nghost = 0;
-  int32_t *d_send_slots = nullptr, *d_rsend = nullptr, *d_rrecv = nullptr;
-  double *pack = nullptr, *rpack = nullptr, *runpack = nullptr;  // send buffer of the ghost exchange; octant buffers of the restriction (64 doubles per item)
+  Dev<int32_t> d_send_slots, d_rsend, d_rrecv;
+  Dev<double> pack, rpack, runpack;  // send buffer of the ghost exchange; octant buffers of the restriction (64 doubles per item)
 };
 // profile entry of one kernel on one level, "mg_smooth@L6": the levels differ by a factor 8 in work, and the roofline of the V-cycle is a
 // statement about the fine ones (bench.py: alt_multigrid.kernels); interned strings, ProfileScope keeps the pointer's text
@@ -71,22 +73,10 @@ static const char *level_name(int kind, int level) {
 }
 struct Multigrid {
   std::vector<MGLevel> lev;  // [0] coarsest ... [L] finest
-  double *zeros = nullptr;   // ghost values behind faces owned by other ranks (see mg_setup); the x pointer itself on one rank
-  double *staged = nullptr;  // uniform grids, in == out (cup3d_preconditioner): the finest level's right-hand side, copied there before the cycle
+  Dev<double> staged;  // uniform grids, in == out (cup3d_preconditioner): the finest level's right-hand side, copied there before the cycle
   bool local = false;        // a rank-local hierarchy (several ranks)
   bool amr = false;          // hierarchy of a multi-level mesh (mg_setup_amr)
   std::shared_ptr<const MGHierarchy> plan;  // ... its tables (kept alive: the exchange plans are read at every cycle)
-  ~Multigrid() {
-    if (zeros) hipFree(zeros);
-    if (staged) hipFree(staged);
-    for (size_t i = 0; i < lev.size(); ++i) {
-      MGLevel &l = lev[i];
-      if ((l.grid || l.own_nbr) && l.d_nbr) hipFree(l.d_nbr);
-      if (l.own_xch) sim_comm_only_destroy(l.xch);
-      void *p[] = {l.d_parent, l.x, l.x2, l.b, l.d_leaf, l.d_cf, l.slabs, l.d_send_slots, l.d_rsend, l.d_rrecv, l.pack, l.rpack, l.runpack};
-      for (void *q : p) if (q) hipFree(q);
-    }
-  }
 };
 
 // `sweeps` red-black Gauss-Seidel sweeps of h (sum6 - 6 x) = b on one block, ghosts from the neighbours' xin (frozen);
@@ -347,11 +337,6 @@ static int mg_setup_amr(Sim *s) {
   mg->local = H.nranks > 1;
   const int nlev = (int)H.lev.size();
   mg->lev.resize(nlev);
-  auto up = [&](int32_t **d, const std::vector<int32_t> &v) -> int {
-    CUP3D_HIP(hipMalloc((void **)d, std::max<size_t>(v.size(), 1) * sizeof(int32_t)));
-    if (!v.empty()) CUP3D_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    return CUP3D_OK;
-  };
   int rc;
   for (int l = 0; l < nlev; ++l) {
     MGLevel &M = mg->lev[l];
@@ -361,28 +346,20 @@ static int mg_setup_amr(Sim *s) {
     M.nb = P.n_owned;
     M.nghost = P.n_ghost;
     M.h = P.h;
-    M.own_nbr = true;
     M.ncf = (int64_t)P.cf.size() / 4;
-    if ((rc = up(&M.d_nbr, P.nbr)) || (rc = up(&M.d_parent, P.parent)) || (rc = up(&M.d_leaf, P.leaf)) || (rc = up(&M.d_cf, P.cf))) return rc;
-    const size_t nvis = (size_t)std::max<int64_t>(P.n_owned + P.n_ghost, 1);
-    const size_t bytes = nvis * 512 * sizeof(double), sb = (size_t)std::max<int64_t>(M.ncf, 1) * 64 * sizeof(double);
-    CUP3D_HIP(hipMalloc((void **)&M.x, bytes));
-    CUP3D_HIP(hipMalloc((void **)&M.x2, bytes));
-    CUP3D_HIP(hipMalloc((void **)&M.b, bytes));
-    CUP3D_HIP(hipMalloc((void **)&M.slabs, sb));
-    CUP3D_HIP(hipMemset(M.slabs, 0, sb));
-    CUP3D_HIP(hipMemset(M.x, 0, bytes));
-    CUP3D_HIP(hipMemset(M.x2, 0, bytes));
-    CUP3D_HIP(hipMemset(M.b, 0, bytes));
-    s->bytes += 3 * bytes + sb;
+    if ((rc = M.own_nbr.upload(P.nbr, IfEmpty::one)) || (rc = M.d_parent.upload(P.parent, IfEmpty::one)) || (rc = M.d_leaf.upload(P.leaf, IfEmpty::one)) || (rc = M.d_cf.upload(P.cf, IfEmpty::one))) return rc;
+    M.d_nbr = M.own_nbr;
+    const size_t nd = (size_t)std::max<int64_t>(P.n_owned + P.n_ghost, 1) * 512, ns = (size_t)std::max<int64_t>(M.ncf, 1) * 64;
+    if ((rc = M.x.alloc(nd, s)) || (rc = M.x2.alloc(nd, s)) || (rc = M.b.alloc(nd, s)) || (rc = M.slabs.alloc(ns, s))) return rc;
+    CUP3D_HIP(hipMemset(M.slabs, 0, M.slabs.bytes()));
+    CUP3D_HIP(hipMemset(M.x, 0, M.x.bytes()));
+    CUP3D_HIP(hipMemset(M.x2, 0, M.x2.bytes()));
+    CUP3D_HIP(hipMemset(M.b, 0, M.b.bytes()));
     if (H.nranks > 1) {
-      if ((rc = up(&M.d_send_slots, P.send_slots)) || (rc = up(&M.d_rsend, P.rsend)) || (rc = up(&M.d_rrecv, P.rrecv))) return rc;
-      const size_t ps = std::max<size_t>(P.send_slots.size(), 1) * 512 * sizeof(double);
-      const size_t rs = std::max<size_t>(P.rsend.size() / 2, 1) * 64 * sizeof(double), rr = std::max<size_t>(P.rrecv.size() / 2, 1) * 64 * sizeof(double);
-      CUP3D_HIP(hipMalloc((void **)&M.pack, ps));
-      CUP3D_HIP(hipMalloc((void **)&M.rpack, rs));
-      CUP3D_HIP(hipMalloc((void **)&M.runpack, rr));
-      s->bytes += ps + rs + rr;
+      if ((rc = M.d_send_slots.upload(P.send_slots, IfEmpty::one)) || (rc = M.d_rsend.upload(P.rsend, IfEmpty::one)) || (rc = M.d_rrecv.upload(P.rrecv, IfEmpty::one)) ||
+          (rc = M.pack.alloc(std::max<size_t>(P.send_slots.size(), 1) * 512, s)) || (rc = M.rpack.alloc(std::max<size_t>(P.rsend.size() / 2, 1) * 64, s)) ||
+          (rc = M.runpack.alloc(std::max<size_t>(P.rrecv.size() / 2, 1) * 64, s)))
+        return rc;
     }
   }
   s->mg = mg.release();
@@ -408,11 +385,6 @@ static int mg_setup(Sim *s) {
   while (lmin > 0 && (N == 1 || (nblocks_at(lmin - 1) % N == 0 && nblocks_at(lmin) % N == 0))) --lmin;
   const int nlev = L - lmin + 1;
   mg->lev.resize(nlev);
-  auto up = [&](int32_t **d, const std::vector<int32_t> &v) -> int {
-    CUP3D_HIP(hipMalloc((void **)d, std::max<size_t>(v.size(), 1) * sizeof(int32_t)));
-    CUP3D_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    return CUP3D_OK;
-  };
   int rc;
   try {
     int64_t max_halo_faces = 0;
@@ -424,21 +396,17 @@ static int mg_setup(Sim *s) {
         M.grid.reset(new Grid(g->bpd, g->level_max, lmin + i, g->maxextent, g->bc, g->rank, N));
         gl = M.grid.get();
         if (N > 1) {
-          M.xch = sim_comm_only(gl, s->comm_stream);
-          M.own_xch = true;
+          M.own_xch.reset(sim_comm_only(gl, s->comm_stream));
+          M.xch = M.own_xch.get();
           if (!M.xch) { set_error("multigrid setup: exchange buffers of level %d", lmin + i); return CUP3D_ENOMEM; }
         }
-        if ((rc = up(&M.d_nbr, gl->nbr))) return rc;
-        const size_t bytes = (size_t)gl->nblocks() * 512 * sizeof(double);
-        CUP3D_HIP(hipMalloc((void **)&M.x, bytes));
-        CUP3D_HIP(hipMalloc((void **)&M.x2, bytes));
-        CUP3D_HIP(hipMalloc((void **)&M.b, bytes));
-        s->bytes += 3 * bytes;
+        const size_t nd = (size_t)gl->nblocks() * 512;
+        if ((rc = M.own_nbr.upload(gl->nbr, IfEmpty::one)) || (rc = M.x.alloc(nd, s)) || (rc = M.x2.alloc(nd, s)) || (rc = M.b.alloc(nd, s))) return rc;
+        M.d_nbr = M.own_nbr;
       } else {
         M.d_nbr = s->d_nbr;
         if (N > 1) M.xch = s;
-        CUP3D_HIP(hipMalloc((void **)&M.x2, (size_t)s->nb * 512 * sizeof(double)));
-        s->bytes += (size_t)s->nb * 512 * sizeof(double);
+        if ((rc = M.x2.alloc((size_t)s->nb * 512, s))) return rc;
       }
       M.nb = gl->nblocks();
       M.h = gl->h;
@@ -455,7 +423,7 @@ static int mg_setup(Sim *s) {
         par[2 * b] = ps;
         par[2 * b + 1] = (ii & 1) + 2 * (j & 1) + 4 * (k & 1);
       }
-      if ((rc = up(&mg->lev[i].d_parent, par))) return rc;
+      if ((rc = mg->lev[i].d_parent.upload(par, IfEmpty::one))) return rc;
     }
   } catch (const std::exception &e) {
     set_error("multigrid setup: %s", e.what());
@@ -621,11 +589,7 @@ int mg_vcycle(Sim *s, const double *in, double *out) {
   if (mg.amr) return mg_vcycle_amr(s, mg, in, out, debug_option("mg_launches") > 0 ? debug_option("mg_launches") : 2, debug_option("mg_sweeps") > 0 ? debug_option("mg_sweeps") : 2);
   const int L = (int)mg.lev.size() - 1;
   if (in == out) {
-    const size_t bytes = (size_t)std::max<int64_t>(s->nb, 1) * 512 * sizeof(double);
-    if (!mg.staged) {
-      CUP3D_HIP(hipMalloc((void **)&mg.staged, bytes));
-      s->bytes += bytes;
-    }
+    if (!mg.staged && (rc = mg.staged.alloc((size_t)std::max<int64_t>(s->nb, 1) * 512, s))) return rc;
     if (s->nb) CUP3D_HIP(hipMemcpyAsync(mg.staged, in, (size_t)s->nb * 512 * sizeof(double), hipMemcpyDeviceToDevice, stream()));
     in = mg.staged;
   }
@@ -641,7 +605,7 @@ int mg_vcycle(Sim *s, const double *in, double *out) {
   }
 
   for (int l = L; l >= 1; --l) {  // downward leg
-    if ((rc = mg_smooth(mg.lev[l], mg.zeros, &xa[l], &xb[l], rhs[l], nu, sw, true))) return rc;
+    if ((rc = mg_smooth(mg.lev[l], nullptr, &xa[l], &xb[l], rhs[l], nu, sw, true))) return rc;
     const GridDev g = level_gdev(mg.lev[l]);
     Sim *xs = mg.lev[l].xch;
     if (xs && (rc = halo_exchange(xs, xa[l], 1, 1))) return rc;
@@ -665,8 +629,8 @@ int mg_vcycle(Sim *s, const double *in, double *out) {
     const double ncells = 512.0 * (double)mg.lev[0].grid->total_blocks;
     hipLaunchKernelGGL(k_mg_sub, dim3(64), dim3(256), 0, stream(), mg.lev[0].b, n, (const double *)tot, 1.0 / ncells);
   }
-  if (mg.lev[0].nb == 1 && !mg.local) rc = mg_smooth(mg.lev[0], mg.zeros, &xa[0], &xb[0], rhs[0], 1, 64, true);
-  else rc = mg_smooth(mg.lev[0], mg.zeros, &xa[0], &xb[0], rhs[0], 16, 4, true);
+  if (mg.lev[0].nb == 1 && !mg.local) rc = mg_smooth(mg.lev[0], nullptr, &xa[0], &xb[0], rhs[0], 1, 64, true);
+  else rc = mg_smooth(mg.lev[0], nullptr, &xa[0], &xb[0], rhs[0], 16, 4, true);
   if (rc) return rc;
   for (int l = 1; l <= L; ++l) {  // upward leg
     {
@@ -674,7 +638,7 @@ int mg_vcycle(Sim *s, const double *in, double *out) {
       hipLaunchKernelGGL(k_mg_prolong_add, dim3((unsigned)mg.lev[l].nb), dim3(256), 0, stream(), (int)mg.lev[l].nb, xa[l], (const int32_t *)mg.lev[l].d_parent,
                          (const double *)xa[l - 1]);
     }
-    if ((rc = mg_smooth(mg.lev[l], mg.zeros, &xa[l], &xb[l], rhs[l], nu, sw, false))) return rc;
+    if ((rc = mg_smooth(mg.lev[l], nullptr, &xa[l], &xb[l], rhs[l], nu, sw, false))) return rc;
   }
   if (xa[L] != out)  // an odd number of buffer swaps on the finest level cannot happen with nu + nu launches, but stay safe
     CUP3D_HIP(hipMemcpyAsync(out, xa[L], (size_t)s->nb * 512 * sizeof(double), hipMemcpyDeviceToDevice, stream()));

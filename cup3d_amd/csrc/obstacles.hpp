@@ -41,21 +41,8 @@ constexpr int kMomentaExplicit = 13;  // penalisation GfX, GpX GpY GpZ, Gj0..Gj5
 // J3..J5 and Gj3..Gj5 are accumulated with -= (13698-13700, 13720-13722)
 constexpr unsigned kMomentaSubtracted = (1u << 10) | (1u << 11) | (1u << 12) | (1u << 20) | (1u << 21) | (1u << 22);
 
-struct DevBuf {
-  void *p = nullptr;
-  size_t size = 0;  // bytes allocated
-  DevBuf() = default;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), size(o.size) { o.p = nullptr; o.size = 0; }  // a retained buffer changes hands (RetainedObstacles)
-  DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(size, o.size); return *this; }
-  int alloc(size_t bytes) { CUP3D_HIP(hipMalloc(&p, bytes ? bytes : 8)); size = bytes ? bytes : 8; return CUP3D_OK; }
-  int upload(const void *src, size_t bytes) {
-    int rc = alloc(bytes);
-    if (rc) return rc;
-    if (bytes) CUP3D_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream()));
-    return CUP3D_OK;
-  }
-  ~DevBuf() { if (p) hipFree(p); }
-};
+// Every device buffer of the obstacle operators is a Dev<void> sized in bytes, allocated and uploaded with IfEmpty::eight_bytes: an obstacle
+// without blocks or surface points still hands the kernels a pointer that is not null.
 
 // ---- host helpers the units share (obstacles_penalization.hip)
 
@@ -64,7 +51,7 @@ struct DevBuf {
 int block_geometry(const Sim *s, const int32_t *slots, long n, std::vector<double> &rows);
 
 // the ObstacleBlocks of one obstacle -> device, freed with the four buffers
-int stage(const Sim *s, const cup3d_obstacle &o, DevBuf &slots, DevBuf &geom, DevBuf &chi, DevBuf &udef, ObstItems *it);
+int stage(const Sim *s, const cup3d_obstacle &o, Dev<void> &slots, Dev<void> &geom, Dev<void> &chi, Dev<void> &udef, ObstItems *it);
 
 // the first `width` columns of rows [n][stride] added in ascending slot order onto total[width]: the reference's loops over
 // obstacleBlocks with one thread
@@ -91,11 +78,11 @@ int sums_over_ranks(Sim *s, double *d_operand, double *v, int n, bool is_max, in
 struct ResidentPlan {
   long rows = 0, nslots = 0;
   std::vector<long> row_base;   // [N + 1]
-  DevBuf obst;                  // ObstItems [N]: the retained slots, geom, chi, udef of every obstacle
-  DevBuf row_obst, row_block;   // int32 [rows]: k and i of a row
-  DevBuf sched_first, sched_rows;  // int32 [nslots + 1], [rows]
-  DevBuf body;                  // double [N][9]: the call's cm, vel, omega of every obstacle
-  DevBuf out;                   // double [rows][29]: the call's block rows ([rows][6] for the penalisation forces)
+  Dev<void> obst;                  // ObstItems [N]: the retained slots, geom, chi, udef of every obstacle
+  Dev<void> row_obst, row_block;   // int32 [rows]: k and i of a row
+  Dev<void> sched_first, sched_rows;  // int32 [nslots + 1], [rows]
+  Dev<void> body;                  // double [N][9]: the call's cm, vel, omega of every obstacle
+  Dev<void> out;                   // double [rows][29]: the call's block rows ([rows][6] for the penalisation forces)
   size_t bytes = 0;
 };
 
@@ -105,7 +92,7 @@ struct RetainedObstacles {
   struct One {
     long nblocks = 0;
     std::vector<int32_t> slots_h;       // the caller's slot list, for the intersections and the plan
-    DevBuf slots, geom, sdf, chi, udef;  // [n], [n][4], [n][10][10][10], [n][8][8][8], [n][8][8][8][3] (corrected)
+    Dev<void> slots, geom, sdf, chi, udef;  // [n], [n][4], [n][10][10][10], [n][8][8][8], [n][8][8][8][3] (corrected)
   };
   std::vector<One> obst;
   ResidentPlan *plan = nullptr;  // nullptr until a resident operator asks for it

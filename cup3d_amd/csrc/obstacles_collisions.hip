@@ -245,23 +245,23 @@ extern "C" int cup3d_prevent_colliding_obstacles(cup3d_sim_t *h, double dt, int 
     std::vector<CollisionObstacle> co(N);
     for (size_t k = 0; k < N; ++k) {
       const RetainedObstacles::One &o = R->obst[k];
-      co[k].geom = (const double *)o.geom.p;
-      co[k].sdf = (const double *)o.sdf.p;
-      co[k].chi = (const double *)o.chi.p;
-      co[k].udef = (const double *)o.udef.p;
+      co[k].geom = o.geom.as<const double>();
+      co[k].sdf = o.sdf.as<const double>();
+      co[k].chi = o.chi.as<const double>();
+      co[k].udef = o.udef.as<const double>();
       for (int d = 0; d < 3; ++d) { co[k].cm[d] = obst[k].cm[d]; co[k].vel[d] = obst[k].vel[d]; co[k].omega[d] = obst[k].omega[d]; }
     }
-    DevBuf d_obst, d_first, d_pairs, d_sums;
-    if ((rc = d_obst.upload(co.data(), N * sizeof(CollisionObstacle))) || (rc = d_first.upload(first.data(), first.size() * sizeof(int32_t))) ||
-        (rc = d_pairs.upload(pairs.data(), pairs.size() * sizeof(int32_t))) || (rc = d_sums.alloc(coll.size() * sizeof(double))))
+    Dev<void> d_obst, d_first, d_pairs, d_sums;
+    if ((rc = d_obst.upload(co.data(), N * sizeof(CollisionObstacle), stream(), IfEmpty::eight_bytes)) || (rc = d_first.upload(first.data(), first.size() * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+        (rc = d_pairs.upload(pairs.data(), pairs.size() * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) || (rc = d_sums.alloc(coll.size() * sizeof(double), IfEmpty::eight_bytes)))
       return rc;
-    const CollisionItems it{(const CollisionObstacle *)d_obst.p, (const int32_t *)d_first.p, (const int32_t *)d_pairs.p, nobst};
+    const CollisionItems it{d_obst.as<const CollisionObstacle>(), d_first.as<const int32_t>(), d_pairs.as<const int32_t>(), nobst};
     {
       ProfileScope ps("collision_sums");
-      hipLaunchKernelGGL(k_collision_sums, dim3((unsigned)N), dim3(64), 0, stream(), it, (double *)d_sums.p);
+      hipLaunchKernelGGL(k_collision_sums, dim3((unsigned)N), dim3(64), 0, stream(), it, d_sums.as<double>());
     }
     CUP3D_HIP(hipGetLastError());
-    CUP3D_HIP(hipMemcpyAsync(coll.data(), d_sums.p, coll.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipMemcpyAsync(coll.data(), d_sums.get(), coll.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
     CUP3D_HIP(hipStreamSynchronize(stream()));  // co, first and pairs are locals
     stats_field_download(coll.size() * sizeof(double));
     return CUP3D_OK;
@@ -276,12 +276,12 @@ extern "C" int cup3d_prevent_colliding_obstacles(cup3d_sim_t *h, double dt, int 
     own_max[2 * i + 1] = c[14] * c[14] + c[15] * c[15] + c[16] * c[16];
   }
   buffermax = own_max;
-  DevBuf red;  // the all-reduce operand of this call: the 2 N maxima and the error flag (sums_over_ranks), then the 20 N sums
+  Dev<void> red;  // the all-reduce operand of this call: the 2 N maxima and the error flag (sums_over_ranks), then the 20 N sums
   if (cross) {
-    const int rc2 = red.alloc(std::max(2 * N + 1, kCollision * N) * sizeof(double));
+    const int rc2 = red.alloc(std::max(2 * N + 1, kCollision * N) * sizeof(double), IfEmpty::eight_bytes);
     if (rc2) return rc ? rc : rc2;
   }
-  if ((rc = sums_over_ranks(s, (double *)red.p, buffermax.data(), (int)(2 * N), true, rc, "cup3d_prevent_colliding_obstacles", -1))) return rc;
+  if ((rc = sums_over_ranks(s, red.as<double>(), buffermax.data(), (int)(2 * N), true, rc, "cup3d_prevent_colliding_obstacles", -1))) return rc;
   for (size_t i = 0; i < N; ++i) {  // 14154-14182
     double *c = &coll[kCollision * i];
     const bool iok = std::fabs(own_max[2 * i] - buffermax[2 * i]) < 1e-10;
@@ -292,7 +292,7 @@ extern "C" int cup3d_prevent_colliding_obstacles(cup3d_sim_t *h, double dt, int 
     }
   }
   if (cross) {  // MPI_SUM of 20 N (14183)
-    double *d = (double *)red.p;
+    double *d = red.as<double>();
     hipStream_t cs = scalar_stream(s);
     int rc2;
     CUP3D_HIP(hipMemcpyAsync(d, coll.data(), coll.size() * sizeof(double), hipMemcpyHostToDevice, cs));

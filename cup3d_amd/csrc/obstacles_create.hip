@@ -225,7 +225,7 @@ int shape_check(const Sim *s, const cup3d_obstacle_shape &o, int k) {
 
 // what one obstacle of a call leaves on the device and on the host until every obstacle of the call has passed
 struct ShapeWork {
-  DevBuf slots, geom, sdf, udef, chi, com, momenta, count, st_ijk, st_dchi, st_delta, first, ijk, dchi, delta;
+  Dev<void> slots, geom, sdf, udef, chi, com, momenta, count, st_ijk, st_dchi, st_delta, first, ijk, dchi, delta;
   ShapeItems it;
   std::vector<double> com_rows, momenta_rows;
   std::vector<int32_t> first_h;
@@ -239,16 +239,16 @@ int characteristic_pass(Sim *s, const cup3d_obstacle_shape &o, long n, int k, Sh
   const size_t nb = (size_t)n;
   std::vector<double> gm;
   int rc;
-  if ((rc = block_geometry(s, o.slots, n, gm)) || (rc = W.slots.upload(o.slots, nb * sizeof(int32_t))) ||
-      (rc = W.geom.upload(gm.data(), gm.size() * sizeof(double))) || (rc = W.sdf.upload(o.sdf, nb * 1000 * sizeof(double))) ||
-      (rc = W.udef.upload(o.udef, nb * 1536 * sizeof(double))) || (rc = W.chi.alloc(nb * 512 * sizeof(double))) ||
-      (rc = W.com.alloc(nb * 4 * sizeof(double))) || (rc = W.momenta.alloc(nb * kUdefMomenta * sizeof(double))) ||
-      (rc = W.count.alloc(nb * sizeof(int32_t))) || (rc = W.st_ijk.alloc(nb * 1536 * sizeof(int32_t))) ||
-      (rc = W.st_dchi.alloc(nb * 1536 * sizeof(double))) || (rc = W.st_delta.alloc(nb * 512 * sizeof(double))))
+  if ((rc = block_geometry(s, o.slots, n, gm)) || (rc = W.slots.upload(o.slots, nb * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+      (rc = W.geom.upload(gm.data(), gm.size() * sizeof(double), stream(), IfEmpty::eight_bytes)) || (rc = W.sdf.upload(o.sdf, nb * 1000 * sizeof(double), stream(), IfEmpty::eight_bytes)) ||
+      (rc = W.udef.upload(o.udef, nb * 1536 * sizeof(double), stream(), IfEmpty::eight_bytes)) || (rc = W.chi.alloc(nb * 512 * sizeof(double), IfEmpty::eight_bytes)) ||
+      (rc = W.com.alloc(nb * 4 * sizeof(double), IfEmpty::eight_bytes)) || (rc = W.momenta.alloc(nb * kUdefMomenta * sizeof(double), IfEmpty::eight_bytes)) ||
+      (rc = W.count.alloc(nb * sizeof(int32_t), IfEmpty::eight_bytes)) || (rc = W.st_ijk.alloc(nb * 1536 * sizeof(int32_t), IfEmpty::eight_bytes)) ||
+      (rc = W.st_dchi.alloc(nb * 1536 * sizeof(double), IfEmpty::eight_bytes)) || (rc = W.st_delta.alloc(nb * 512 * sizeof(double), IfEmpty::eight_bytes)))
     return rc;
   CUP3D_HIP(hipStreamSynchronize(stream()));  // gm is a local
-  W.it = ShapeItems{(const int32_t *)W.slots.p, (const double *)W.geom.p, (const double *)W.sdf.p, (double *)W.udef.p, (double *)W.chi.p, (double *)W.com.p,
-                    (double *)W.momenta.p, (int32_t *)W.count.p, (int32_t *)W.st_ijk.p, (double *)W.st_dchi.p, (double *)W.st_delta.p};
+  W.it = ShapeItems{W.slots.as<const int32_t>(), W.geom.as<const double>(), W.sdf.as<const double>(), W.udef.as<double>(), W.chi.as<double>(), W.com.as<double>(),
+                    W.momenta.as<double>(), W.count.as<int32_t>(), W.st_ijk.as<int32_t>(), W.st_dchi.as<double>(), W.st_delta.as<double>()};
   {
     ProfileScope ps("characteristic");
     hipLaunchKernelGGL(k_characteristic, dim3((unsigned)n), dim3(64), 0, stream(), W.it, s->chi);
@@ -256,8 +256,8 @@ int characteristic_pass(Sim *s, const cup3d_obstacle_shape &o, long n, int k, Sh
   CUP3D_HIP(hipGetLastError());
   W.com_rows.resize(nb * 4);
   std::vector<int32_t> count(nb);
-  CUP3D_HIP(hipMemcpyAsync(W.com_rows.data(), W.com.p, nb * 4 * sizeof(double), hipMemcpyDeviceToHost, stream()));
-  CUP3D_HIP(hipMemcpyAsync(count.data(), W.count.p, nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
+  CUP3D_HIP(hipMemcpyAsync(W.com_rows.data(), W.com.get(), nb * 4 * sizeof(double), hipMemcpyDeviceToHost, stream()));
+  CUP3D_HIP(hipMemcpyAsync(count.data(), W.count.get(), nb * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
   CUP3D_HIP(hipStreamSynchronize(stream()));
   stats_field_download(nb * (4 * sizeof(double) + sizeof(int32_t)));
   for (size_t i = 0; i < nb; ++i) {
@@ -265,13 +265,13 @@ int characteristic_pass(Sim *s, const cup3d_obstacle_shape &o, long n, int k, Sh
     W.first_h[i + 1] = W.first_h[i] + count[i];
   }
   const size_t np = (size_t)W.first_h[nb];
-  if ((rc = W.first.upload(W.first_h.data(), (nb + 1) * sizeof(int32_t))) || (rc = W.ijk.alloc(np * 3 * sizeof(int32_t))) ||
-      (rc = W.dchi.alloc(np * 3 * sizeof(double))) || (rc = W.delta.alloc(np * sizeof(double))))
+  if ((rc = W.first.upload(W.first_h.data(), (nb + 1) * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) || (rc = W.ijk.alloc(np * 3 * sizeof(int32_t), IfEmpty::eight_bytes)) ||
+      (rc = W.dchi.alloc(np * 3 * sizeof(double), IfEmpty::eight_bytes)) || (rc = W.delta.alloc(np * sizeof(double), IfEmpty::eight_bytes)))
     return rc;
   {
     ProfileScope ps("pack_surface");
-    hipLaunchKernelGGL(k_pack_surface, dim3((unsigned)n), dim3(64), 0, stream(), W.it, (const int32_t *)W.first.p, (int32_t *)W.ijk.p, (double *)W.dchi.p,
-                       (double *)W.delta.p);
+    hipLaunchKernelGGL(k_pack_surface, dim3((unsigned)n), dim3(64), 0, stream(), W.it, W.first.as<const int32_t>(), W.ijk.as<int32_t>(), W.dchi.as<double>(),
+                       W.delta.as<double>());
   }
   CUP3D_HIP(hipGetLastError());
   add_rows_in_slot_order(o.slots, n, W.com_rows.data(), 4, 4, W.com_totals);
@@ -288,7 +288,7 @@ int momenta_pass(Sim *s, const cup3d_obstacle_shape &o, long n, ShapeWork &W) {
   }
   CUP3D_HIP(hipGetLastError());
   W.momenta_rows.resize((size_t)n * kUdefMomenta);
-  CUP3D_HIP(hipMemcpyAsync(W.momenta_rows.data(), W.momenta.p, W.momenta_rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+  CUP3D_HIP(hipMemcpyAsync(W.momenta_rows.data(), W.momenta.get(), W.momenta_rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
   CUP3D_HIP(hipStreamSynchronize(stream()));
   stats_field_download(W.momenta_rows.size() * sizeof(double));
   add_rows_in_slot_order(o.slots, n, W.momenta_rows.data(), kUdefMomenta, kUdefMomenta, W.M);
@@ -299,12 +299,12 @@ int momenta_pass(Sim *s, const cup3d_obstacle_shape &o, long n, ShapeWork &W) {
 int shape_copy_out(cup3d_obstacle_shape &o, const ShapeWork &W) {
   const size_t nb = (size_t)o.nblocks, np = (size_t)W.first_h[nb];
   if (nb) {
-    CUP3D_HIP(hipMemcpyAsync(o.chi, W.chi.p, nb * 512 * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    CUP3D_HIP(hipMemcpyAsync(o.udef, W.udef.p, nb * 1536 * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipMemcpyAsync(o.chi, W.chi.get(), nb * 512 * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipMemcpyAsync(o.udef, W.udef.get(), nb * 1536 * sizeof(double), hipMemcpyDeviceToHost, stream()));
     if (np) {
-      CUP3D_HIP(hipMemcpyAsync(o.ijk, W.ijk.p, np * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
-      CUP3D_HIP(hipMemcpyAsync(o.dchi, W.dchi.p, np * 3 * sizeof(double), hipMemcpyDeviceToHost, stream()));
-      CUP3D_HIP(hipMemcpyAsync(o.delta, W.delta.p, np * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipMemcpyAsync(o.ijk, W.ijk.get(), np * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipMemcpyAsync(o.dchi, W.dchi.get(), np * 3 * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipMemcpyAsync(o.delta, W.delta.get(), np * sizeof(double), hipMemcpyDeviceToHost, stream()));
     }
     CUP3D_HIP(hipStreamSynchronize(stream()));
     stats_field_download(nb * 2048 * sizeof(double) + np * (3 * sizeof(int32_t) + 4 * sizeof(double)));
@@ -338,9 +338,9 @@ int create_obstacles(Sim *s, int nobst, cup3d_obstacle_shape *shapes, std::vecto
   for (int k = 0; k < nobst && !bad; ++k) bad = shape_check(s, shapes[k], k);
   if (bad && !cross) return bad;
   const std::string bad_text = bad ? cup3d_last_error() : "";
-  DevBuf red;  // the all-reduce operand of this call (sums_over_ranks): up to 13 totals and the error flag
+  Dev<void> red;  // the all-reduce operand of this call (sums_over_ranks): up to 13 totals and the error flag
   int rc;
-  if (cross && (rc = red.alloc((kUdefMomenta + 1) * sizeof(double)))) return rc;
+  if (cross && (rc = red.alloc((kUdefMomenta + 1) * sizeof(double), IfEmpty::eight_bytes))) return rc;
   if (!bad) {  // CHI.clear() of every block (13596-13600)
     CUP3D_HIP(hipMemsetAsync(s->chi, 0, (size_t)s->nb * 512 * sizeof(double), stream()));
     s->chi_nonzero = true;
@@ -352,7 +352,7 @@ int create_obstacles(Sim *s, int nobst, cup3d_obstacle_shape *shapes, std::vecto
     for (int q = 0; q < 4; ++q) W.com_totals[q] = 0.0;
     for (int q = 0; q < kUdefMomenta; ++q) W.M[q] = 0.0;
     W.first_h.assign((size_t)n + 1, 0);
-    rc = sums_over_ranks(s, (double *)red.p, W.com_totals, 4, false, bad ? bad : characteristic_pass(s, o, n, k, W), who, k);  // MPI_Allreduce(com, 4), 13419
+    rc = sums_over_ranks(s, red.as<double>(), W.com_totals, 4, false, bad ? bad : characteristic_pass(s, o, n, k, W), who, k);  // MPI_Allreduce(com, 4), 13419
     if (rc) {
       if (bad) set_error("%s", bad_text.c_str());
       return rc;
@@ -365,7 +365,7 @@ int create_obstacles(Sim *s, int nobst, cup3d_obstacle_shape *shapes, std::vecto
       W.cm[d] = W.com_totals[1 + d] / W.com_totals[0];
       W.transvel[d] = o.transvel_correction[d];  // oldCorrVel, 13436
     }
-    if ((rc = sums_over_ranks(s, (double *)red.p, W.M, kUdefMomenta, false, momenta_pass(s, o, n, W), who, k))) return rc;  // MPI_Allreduce(M, 13), 13519
+    if ((rc = sums_over_ranks(s, red.as<double>(), W.M, kUdefMomenta, false, momenta_pass(s, o, n, W), who, k))) return rc;  // MPI_Allreduce(M, 13), 13519
     if (!(W.M[0] > DBL_EPSILON)) {  // assert(M[0] > EPS), 13520
       set_error("cup3d_create_obstacles: obstacle %d has volume %g under chi > 0", k, W.M[0]);
       return CUP3D_EINVAL;
@@ -395,7 +395,7 @@ int create_obstacles(Sim *s, int nobst, cup3d_obstacle_shape *shapes, std::vecto
 void retained_destroy(Sim *s) {
   if (!s->retained) return;
   s->bytes -= s->retained->bytes;
-  delete s->retained;  // DevBuf frees
+  delete s->retained;  // Dev<void> frees
   s->retained = nullptr;
 }
 
@@ -424,7 +424,7 @@ int resident_plan(Sim *s, RetainedObstacles *R, ResidentPlan **out) {
     std::vector<int32_t> row_obst(nr), row_block(nr), row_slot(nr), sched_rows(nr), sched_first;
     for (size_t k = 0; k < N; ++k) {
       const RetainedObstacles::One &o = R->obst[k];
-      items[k] = ObstItems{(const int32_t *)o.slots.p, (const double *)o.geom.p, (const double *)o.chi.p, (const double *)o.udef.p};
+      items[k] = ObstItems{o.slots.as<const int32_t>(), o.geom.as<const double>(), o.chi.as<const double>(), o.udef.as<const double>()};
       for (long i = 0; i < o.nblocks; ++i) {
         const size_t r = (size_t)(P->row_base[k] + i);
         row_obst[r] = (int32_t)k;
@@ -440,13 +440,13 @@ int resident_plan(Sim *s, RetainedObstacles *R, ResidentPlan **out) {
     P->nslots = (long)sched_first.size();
     sched_first.push_back((int32_t)nr);
     int rc;
-    if ((rc = P->obst.upload(items.data(), N * sizeof(ObstItems))) || (rc = P->row_obst.upload(row_obst.data(), nr * sizeof(int32_t))) ||
-        (rc = P->row_block.upload(row_block.data(), nr * sizeof(int32_t))) || (rc = P->sched_first.upload(sched_first.data(), sched_first.size() * sizeof(int32_t))) ||
-        (rc = P->sched_rows.upload(sched_rows.data(), nr * sizeof(int32_t))) || (rc = P->body.alloc(N * 9 * sizeof(double))) ||
-        (rc = P->out.alloc(nr * kMomenta * sizeof(double))))
+    if ((rc = P->obst.upload(items.data(), N * sizeof(ObstItems), stream(), IfEmpty::eight_bytes)) || (rc = P->row_obst.upload(row_obst.data(), nr * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+        (rc = P->row_block.upload(row_block.data(), nr * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) || (rc = P->sched_first.upload(sched_first.data(), sched_first.size() * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+        (rc = P->sched_rows.upload(sched_rows.data(), nr * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) || (rc = P->body.alloc(N * 9 * sizeof(double), IfEmpty::eight_bytes)) ||
+        (rc = P->out.alloc(nr * kMomenta * sizeof(double), IfEmpty::eight_bytes)))
       return rc;
     CUP3D_HIP(hipStreamSynchronize(stream()));  // the tables are locals
-    P->bytes = P->obst.size + P->row_obst.size + P->row_block.size + P->sched_first.size + P->sched_rows.size + P->body.size + P->out.size;
+    P->bytes = P->obst.bytes() + P->row_obst.bytes() + P->row_block.bytes() + P->sched_first.bytes() + P->sched_rows.bytes() + P->body.bytes() + P->out.bytes();
   }
   drop.p = nullptr;
   R->plan = P;
@@ -457,8 +457,8 @@ int resident_plan(Sim *s, RetainedObstacles *R, ResidentPlan **out) {
 }
 
 PlanItems plan_items(const ResidentPlan *P) {
-  return PlanItems{(const ObstItems *)P->obst.p, (const int32_t *)P->row_obst.p, (const int32_t *)P->row_block.p, (const int32_t *)P->sched_first.p,
-                   (const int32_t *)P->sched_rows.p, (const double *)P->body.p};
+  return PlanItems{P->obst.as<const ObstItems>(), P->row_obst.as<const int32_t>(), P->row_block.as<const int32_t>(), P->sched_first.as<const int32_t>(),
+                   P->sched_rows.as<const int32_t>(), P->body.as<const double>()};
 }
 
 }  // namespace cup3d
@@ -489,7 +489,7 @@ extern "C" int cup3d_create_obstacles(cup3d_sim_t *h, int nobst, cup3d_obstacle_
     o.sdf = std::move(W.sdf);
     o.chi = std::move(W.chi);
     o.udef = std::move(W.udef);
-    R->bytes += o.slots.size + o.geom.size + o.sdf.size + o.chi.size + o.udef.size;
+    R->bytes += o.slots.bytes() + o.geom.bytes() + o.sdf.bytes() + o.chi.bytes() + o.udef.bytes();
   }
   s->retained = R;
   s->bytes += R->bytes;

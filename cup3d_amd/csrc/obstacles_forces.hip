@@ -207,34 +207,13 @@ __global__ void __launch_bounds__(64) k_surface_forces(SurfItems it, const doubl
 // device buffers of cup3d_compute_forces, kept in the sim and only ever grown: the tile scratch of one chunk of blocks and the staged
 // arrays of one obstacle
 struct ForcesScratch {
-  struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int need(size_t bytes, Sim *s) {
-      if (bytes <= cap) return CUP3D_OK;
-      if (p) { (void)hipFree(p); s->bytes -= cap; p = nullptr; cap = 0; }
-      CUP3D_HIP(hipMalloc(&p, bytes));
-      cap = bytes;
-      s->bytes += bytes;
-      return CUP3D_OK;
-    }
-    int upload(const void *src, size_t bytes, Sim *s) {
-      int rc = need(bytes ? bytes : 8, s);
-      if (rc) return rc;
-      if (bytes) CUP3D_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream()));
-      return CUP3D_OK;
-    }
-  };
-  Buf vel, chi, slots, geom, first, ijk, dchi, udef, points, qoi;
+  DevGrow vel, chi, slots, geom, first, ijk, dchi, udef, points, qoi;
 };
 
 void forces_destroy(Sim *s) {
   ForcesScratch *F = s->forces;
   if (!F) return;
-  ForcesScratch::Buf *all[] = {&F->vel, &F->chi, &F->slots, &F->geom, &F->first, &F->ijk, &F->dchi, &F->udef, &F->points, &F->qoi};
-  for (ForcesScratch::Buf *b : all)
-    if (b->p) { (void)hipFree(b->p); s->bytes -= b->cap; }
-  delete F;
+  delete F;  // the buffers take their bytes off the ledger
   s->forces = nullptr;
 }
 
@@ -273,15 +252,15 @@ int surface_stage(Sim *s, const cup3d_obstacle_surface &o, SurfItems *it) {
   const size_t nb = (size_t)o.nblocks, np = (size_t)o.first[o.nblocks];
   std::vector<double> gm;
   int rc;
-  if ((rc = block_geometry(s, o.slots, o.nblocks, gm)) || (rc = F->slots.upload(o.slots, nb * sizeof(int32_t), s)) ||
-      (rc = F->geom.upload(gm.data(), gm.size() * sizeof(double), s)) ||
-      (rc = F->first.upload(o.first, (nb + 1) * sizeof(int32_t), s)) || (rc = F->ijk.upload(o.ijk, np * 3 * sizeof(int32_t), s)) ||
-      (rc = F->dchi.upload(o.dchi, np * 3 * sizeof(double), s)) || (rc = F->udef.upload(o.udef, nb * 1536 * sizeof(double), s)) ||
-      (rc = F->qoi.upload(o.qoi, nb * kQoI * sizeof(double), s)) || (rc = F->points.need(std::max<size_t>(np, 1) * kQoI * sizeof(double), s)))
+  if ((rc = block_geometry(s, o.slots, o.nblocks, gm)) || (rc = F->slots.upload(o.slots, nb * sizeof(int32_t), 8, stream(), s)) ||
+      (rc = F->geom.upload(gm.data(), gm.size() * sizeof(double), 8, stream(), s)) ||
+      (rc = F->first.upload(o.first, (nb + 1) * sizeof(int32_t), 8, stream(), s)) || (rc = F->ijk.upload(o.ijk, np * 3 * sizeof(int32_t), 8, stream(), s)) ||
+      (rc = F->dchi.upload(o.dchi, np * 3 * sizeof(double), 8, stream(), s)) || (rc = F->udef.upload(o.udef, nb * 1536 * sizeof(double), 8, stream(), s)) ||
+      (rc = F->qoi.upload(o.qoi, nb * kQoI * sizeof(double), 8, stream(), s)) || (rc = F->points.need(std::max<size_t>(np, 1) * kQoI * sizeof(double), s)))
     return rc;
   CUP3D_HIP(hipStreamSynchronize(stream()));  // gm is a local
-  *it = SurfItems{(const int32_t *)F->slots.p, (const double *)F->geom.p, (const int32_t *)F->first.p, (const int32_t *)F->ijk.p, (const double *)F->dchi.p,
-                  (const double *)F->udef.p, (const double *)F->vel.p, (const double *)F->chi.p, (double *)F->points.p, (double *)F->qoi.p, (long)np};
+  *it = SurfItems{F->slots.as<const int32_t>(), F->geom.as<const double>(), F->first.as<const int32_t>(), F->ijk.as<const int32_t>(), F->dchi.as<const double>(),
+                  F->udef.as<const double>(), F->vel.as<const double>(), F->chi.as<const double>(), F->points.as<double>(), F->qoi.as<double>(), (long)np};
   return CUP3D_OK;
 }
 
@@ -304,8 +283,8 @@ int surface_download(Sim *s, const cup3d_obstacle_surface &o) {
   const size_t nb = (size_t)o.nblocks, np = (size_t)o.first[o.nblocks];
   {
     ProfileScope ps("surface_forces_download");
-    if (np) CUP3D_HIP(hipMemcpyAsync(o.points, F->points.p, np * kQoI * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    CUP3D_HIP(hipMemcpyAsync(o.qoi, F->qoi.p, nb * kQoI * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    if (np) CUP3D_HIP(hipMemcpyAsync(o.points, F->points.get(), np * kQoI * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipMemcpyAsync(o.qoi, F->qoi.get(), nb * kQoI * sizeof(double), hipMemcpyDeviceToHost, stream()));
   }
   CUP3D_HIP(hipStreamSynchronize(stream()));
   stats_field_download((np + nb) * kQoI * sizeof(double));
@@ -342,8 +321,8 @@ extern "C" int cup3d_compute_forces(cup3d_sim_t *h, double nu, int nobst, cup3d_
     if ((rc = scratch_for(s, std::min(chunk, o.nblocks))) || (rc = surface_stage(s, o, &it))) return rc;
     for (long t0 = 0; t0 < o.nblocks; t0 += chunk) {
       const long m = std::min(chunk, o.nblocks - t0);
-      if ((rc = cup3d_sim_labs_device(h, CUP3D_FIELD_VEL, m, o.slots + t0, 4, 1, -1, s->forces->vel.p)) ||
-          (rc = cup3d_sim_labs_device(h, CUP3D_FIELD_CHI, m, o.slots + t0, 4, 1, -1, s->forces->chi.p)) || (rc = surface_launch(s, o, it, t0, m, nu)))
+      if ((rc = cup3d_sim_labs_device(h, CUP3D_FIELD_VEL, m, o.slots + t0, 4, 1, -1, s->forces->vel.get())) ||
+          (rc = cup3d_sim_labs_device(h, CUP3D_FIELD_CHI, m, o.slots + t0, 4, 1, -1, s->forces->chi.get())) || (rc = surface_launch(s, o, it, t0, m, nu)))
         return rc;
     }
     if ((rc = surface_download(s, o))) return rc;
@@ -385,8 +364,8 @@ extern "C" int cup3d_compute_forces_over_ranks(cup3d_sim_t *h, const cup3d_grid_
     if (nblocks && ((rc = scratch_for(s, std::min(chunk, nblocks))) || (rc = surface_stage(s, o, &it)))) return rc;
     for (long r = 0; r < rounds; ++r) {
       const long t0 = r * chunk, m = std::max(0L, std::min(chunk, nblocks - t0));
-      if ((rc = cup3d_sim_labs_over_ranks_device(h, mesh, owner, CUP3D_FIELD_VEL, m, m ? o.slots + t0 : nullptr, 4, 1, -1, m ? s->forces->vel.p : nullptr)) ||
-          (rc = cup3d_sim_labs_over_ranks_device(h, mesh, owner, CUP3D_FIELD_CHI, m, m ? o.slots + t0 : nullptr, 4, 1, -1, m ? s->forces->chi.p : nullptr)))
+      if ((rc = cup3d_sim_labs_over_ranks_device(h, mesh, owner, CUP3D_FIELD_VEL, m, m ? o.slots + t0 : nullptr, 4, 1, -1, m ? s->forces->vel.get() : nullptr)) ||
+          (rc = cup3d_sim_labs_over_ranks_device(h, mesh, owner, CUP3D_FIELD_CHI, m, m ? o.slots + t0 : nullptr, 4, 1, -1, m ? s->forces->chi.get() : nullptr)))
         return rc;
       if (m && (rc = surface_launch(s, o, it, t0, m, nu))) return rc;
     }

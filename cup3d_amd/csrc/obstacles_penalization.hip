@@ -113,18 +113,18 @@ int block_geometry(const Sim *s, const int32_t *slots, long n, std::vector<doubl
   return CUP3D_OK;
 }
 
-int stage(const Sim *s, const cup3d_obstacle &o, DevBuf &slots, DevBuf &geom, DevBuf &chi, DevBuf &udef, ObstItems *it) {
+int stage(const Sim *s, const cup3d_obstacle &o, Dev<void> &slots, Dev<void> &geom, Dev<void> &chi, Dev<void> &udef, ObstItems *it) {
   std::vector<double> gm;
   int rc;
-  if ((rc = block_geometry(s, o.slots, o.nblocks, gm)) || (rc = slots.upload(o.slots, o.nblocks * sizeof(int32_t))) ||
-      (rc = geom.upload(gm.data(), gm.size() * sizeof(double))) || (rc = chi.upload(o.chi, (size_t)o.nblocks * 512 * sizeof(double))) ||
-      (rc = udef.upload(o.udef, (size_t)o.nblocks * 1536 * sizeof(double))))
+  if ((rc = block_geometry(s, o.slots, o.nblocks, gm)) || (rc = slots.upload(o.slots, o.nblocks * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+      (rc = geom.upload(gm.data(), gm.size() * sizeof(double), stream(), IfEmpty::eight_bytes)) || (rc = chi.upload(o.chi, (size_t)o.nblocks * 512 * sizeof(double), stream(), IfEmpty::eight_bytes)) ||
+      (rc = udef.upload(o.udef, (size_t)o.nblocks * 1536 * sizeof(double), stream(), IfEmpty::eight_bytes)))
     return rc;
   CUP3D_HIP(hipStreamSynchronize(stream()));  // gm is a local
-  it->slots = (const int32_t *)slots.p;
-  it->geom = (const double *)geom.p;
-  it->chi = (const double *)chi.p;
-  it->udef = (const double *)udef.p;
+  it->slots = slots.as<const int32_t>();
+  it->geom = geom.as<const double>();
+  it->chi = chi.as<const double>();
+  it->udef = udef.as<const double>();
   return CUP3D_OK;
 }
 
@@ -197,18 +197,18 @@ extern "C" int cup3d_penalization(cup3d_sim_t *h, double dt, double lambda, int 
       if (o.nblocks <= 0) return CUP3D_OK;
       int rc;
       if (!o.slots || !o.chi || !o.udef) { set_error("cup3d_penalization: obstacle %d has blocks but no slots / chi / udef", k); return CUP3D_EINVAL; }
-      DevBuf slots, geom, chi, udef, forces;
+      Dev<void> slots, geom, chi, udef, forces;
       ObstItems it;
       if ((rc = stage(s, o, slots, geom, chi, udef, &it))) return rc;
-      if ((rc = forces.alloc((size_t)o.nblocks * 6 * sizeof(double)))) return rc;
+      if ((rc = forces.alloc((size_t)o.nblocks * 6 * sizeof(double), IfEmpty::eight_bytes))) return rc;
       {
         ProfileScope ps("penalization");
         hipLaunchKernelGGL(k_penalize, dim3((unsigned)o.nblocks), dim3(256), 0, stream(), it, s->vel, s->chi, dt, lambdaFac, implicit ? 1 : 0, o.cm[0], o.cm[1],
-                           o.cm[2], o.vel[0], o.vel[1], o.vel[2], o.omega[0], o.omega[1], o.omega[2], (double *)forces.p);
+                           o.cm[2], o.vel[0], o.vel[1], o.vel[2], o.omega[0], o.omega[1], o.omega[2], forces.as<double>());
       }
       CUP3D_HIP(hipGetLastError());
       std::vector<double> F((size_t)o.nblocks * 6);
-      CUP3D_HIP(hipMemcpyAsync(F.data(), forces.p, F.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipMemcpyAsync(F.data(), forces.get(), F.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
       CUP3D_HIP(hipStreamSynchronize(stream()));
       // kernelFinalizePenalizationForce (13913-13938): block totals in block (slot) order
       add_rows_in_slot_order(o.slots, o.nblocks, F.data(), 6, 6, M);
@@ -228,7 +228,7 @@ extern "C" int cup3d_update_tmpv(cup3d_sim_t *h, int nobst, const cup3d_obstacle
     const cup3d_obstacle &o = obst[k];
     if (o.nblocks <= 0) continue;
     if (!o.slots || !o.chi || !o.udef) return CUP3D_EINVAL;
-    DevBuf slots, geom, chi, udef;
+    Dev<void> slots, geom, chi, udef;
     ObstItems it;
     int rc = stage(s, o, slots, geom, chi, udef, &it);
     if (rc) return rc;
@@ -261,15 +261,15 @@ extern "C" int cup3d_penalization_resident(cup3d_sim_t *h, double dt, double lam
         table[9 * (size_t)k + 3 + d] = body[k].vel[d];
         table[9 * (size_t)k + 6 + d] = body[k].omega[d];
       }
-    CUP3D_HIP(hipMemcpyAsync(P->body.p, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
+    CUP3D_HIP(hipMemcpyAsync(P->body.get(), table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
     {
       ProfileScope ps("penalization_set");
       hipLaunchKernelGGL(k_penalize_set, dim3((unsigned)P->nslots), dim3(256), 0, stream(), plan_items(P), s->vel, (const double *)s->chi, dt, lambdaFac,
-                         implicit ? 1 : 0, (double *)P->out.p);
+                         implicit ? 1 : 0, P->out.as<double>());
     }
     CUP3D_HIP(hipGetLastError());
     F.resize((size_t)P->rows * 6);
-    CUP3D_HIP(hipMemcpyAsync(F.data(), P->out.p, F.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipMemcpyAsync(F.data(), P->out.get(), F.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
     CUP3D_HIP(hipStreamSynchronize(stream()));
     stats_field_download(F.size() * sizeof(double));
     return CUP3D_OK;

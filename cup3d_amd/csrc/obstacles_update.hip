@@ -215,9 +215,9 @@ extern "C" int cup3d_update_obstacles(cup3d_sim_t *h, double dt, double lambda, 
   std::vector<MomentaResult> res((size_t)nobst);
   std::vector<std::vector<double>> rows((size_t)nobst);
   const bool cross = scalars_cross_ranks(s);
-  DevBuf red;  // the all-reduce operand of this call (sums_over_ranks)
+  Dev<void> red;  // the all-reduce operand of this call (sums_over_ranks)
   if (cross && nobst > 0) {
-    int rc = red.alloc((kMomenta + 1) * sizeof(double));
+    int rc = red.alloc((kMomenta + 1) * sizeof(double), IfEmpty::eight_bytes);
     if (rc) return rc;
   }
   for (int k = 0; k < nobst; ++k) {  // obstacles one after the other, as kernelFinalizeObstacleVel visits them (13739)
@@ -231,18 +231,18 @@ extern "C" int cup3d_update_obstacles(cup3d_sim_t *h, double dt, double lambda, 
       if (o.nblocks == 0) return CUP3D_OK;
       int rc;
       if (!o.slots || !o.chi || !o.udef) { set_error("cup3d_update_obstacles: obstacle %d has blocks but no slots / chi / udef", k); return CUP3D_EINVAL; }
-      DevBuf slots, geom, chi, udef, sums;
+      Dev<void> slots, geom, chi, udef, sums;
       ObstItems it;
       if ((rc = stage(s, o, slots, geom, chi, udef, &it))) return rc;
-      if ((rc = sums.alloc((size_t)o.nblocks * kMomenta * sizeof(double)))) return rc;
+      if ((rc = sums.alloc((size_t)o.nblocks * kMomenta * sizeof(double), IfEmpty::eight_bytes))) return rc;
       {
         ProfileScope ps("update_obstacles");
         hipLaunchKernelGGL(k_fluid_momenta, dim3((unsigned)o.nblocks), dim3(64), 0, stream(), it, (const double *)s->vel, lambdt, implicit ? 1 : 0, o.cm[0], o.cm[1],
-                           o.cm[2], (double *)sums.p);
+                           o.cm[2], sums.as<double>());
       }
       CUP3D_HIP(hipGetLastError());
       rows[k].resize((size_t)o.nblocks * kMomenta);
-      CUP3D_HIP(hipMemcpyAsync(rows[k].data(), sums.p, rows[k].size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+      CUP3D_HIP(hipMemcpyAsync(rows[k].data(), sums.get(), rows[k].size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
       CUP3D_HIP(hipStreamSynchronize(stream()));
       stats_field_download(rows[k].size() * sizeof(double));
       R.rows = rows[k].data();
@@ -251,7 +251,7 @@ extern "C" int cup3d_update_obstacles(cup3d_sim_t *h, double dt, double lambda, 
       add_rows_in_slot_order(o.slots, o.nblocks, R.rows, kMomenta, nq, M);
       return CUP3D_OK;
     };
-    int rc = obstacle_motion_from_sums(s, "cup3d_update_obstacles", k, local_part(), (double *)red.p, implicit, motion[k], R);
+    int rc = obstacle_motion_from_sums(s, "cup3d_update_obstacles", k, local_part(), red.as<double>(), implicit, motion[k], R);
     if (rc) return rc;
   }
   for (int k = 0; k < nobst; ++k) write_obstacle_motion(res[k], nq, motion[k], obst[k].vel, obst[k].omega);
@@ -268,9 +268,9 @@ extern "C" int cup3d_update_obstacles_resident(cup3d_sim_t *h, double dt, double
   // nothing of the caller's is written before every obstacle of the call has passed: the results wait here
   std::vector<MomentaResult> res((size_t)nobst);
   std::vector<double> rows, table;
-  DevBuf red;  // the all-reduce operand of this call (sums_over_ranks)
+  Dev<void> red;  // the all-reduce operand of this call (sums_over_ranks)
   if (scalars_cross_ranks(s)) {
-    int rc = red.alloc((kMomenta + 1) * sizeof(double));
+    int rc = red.alloc((kMomenta + 1) * sizeof(double), IfEmpty::eight_bytes);
     if (rc) return rc;
   }
   RetainedObstacles *R = nullptr;
@@ -283,15 +283,15 @@ extern "C" int cup3d_update_obstacles_resident(cup3d_sim_t *h, double dt, double
     table.assign(9 * (size_t)nobst, 0.0);
     for (int k = 0; k < nobst; ++k)
       for (int d = 0; d < 3; ++d) table[9 * (size_t)k + d] = body[k].cm[d];
-    CUP3D_HIP(hipMemcpyAsync(P->body.p, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
+    CUP3D_HIP(hipMemcpyAsync(P->body.get(), table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
     {
       ProfileScope ps("update_obstacles_set");
       hipLaunchKernelGGL(k_fluid_momenta_set, dim3((unsigned)P->rows), dim3(64), 0, stream(), plan_items(P), (const double *)s->vel, lambdt, implicit ? 1 : 0,
-                         (double *)P->out.p);
+                         P->out.as<double>());
     }
     CUP3D_HIP(hipGetLastError());
     rows.resize((size_t)P->rows * kMomenta);
-    CUP3D_HIP(hipMemcpyAsync(rows.data(), P->out.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    CUP3D_HIP(hipMemcpyAsync(rows.data(), P->out.get(), rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
     CUP3D_HIP(hipStreamSynchronize(stream()));
     stats_field_download(rows.size() * sizeof(double));
     return CUP3D_OK;
@@ -307,7 +307,7 @@ extern "C" int cup3d_update_obstacles_resident(cup3d_sim_t *h, double dt, double
       // kernelFinalizeObstacleVel's loop with one thread (13744-13781): block rows in block (slot) order
       add_rows_in_slot_order(R->obst[k].slots_h.data(), Q.nblocks, Q.rows, kMomenta, nq, Q.M);
     }
-    int rc = obstacle_motion_from_sums(s, "cup3d_update_obstacles_resident", k, local, (double *)red.p, implicit, motion[k], Q);
+    int rc = obstacle_motion_from_sums(s, "cup3d_update_obstacles_resident", k, local, red.as<double>(), implicit, motion[k], Q);
     if (rc) return rc;
   }
   for (int k = 0; k < nobst; ++k) write_obstacle_motion(res[k], nq, motion[k], body[k].vel, body[k].omega);

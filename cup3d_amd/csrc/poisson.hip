@@ -35,49 +35,32 @@
 namespace cup3d {
 
 static int ensure_vectors(Sim *s) {
-  if (!s->d_block_dots) {
-    int rc = sim_alloc(&s->d_block_dots, (size_t)7 * s->nb, s);
-    if (rc) return rc;
-  }
+  int rc;
+  if (!s->d_block_dots && (rc = s->d_block_dots.alloc_zeroed((size_t)7 * s->nb, stream(), s))) return rc;
   // Arrive: [dots | mean] x (n1 + n2 + 1) counters + 2 flags; (7 + 1) x (n1 + n2) partial sums.  Each allocation is guarded by its OWN
   // pointer (one guard over four allocations left the later ones null for ever when one of them failed once)
   {
     const size_t n1 = ((size_t)s->nb + 63) / 64, n2 = (n1 + 63) / 64, ncnt = 2 * (n1 + n2 + 1) + 2;
-    if (!s->d_arrive_sums) {
-      int rc = sim_alloc(&s->d_arrive_sums, 8 * (n1 + n2) + 8, s);
-      if (rc) return rc;
-    }
-    if (!s->d_arrive) {
-      CUP3D_HIP(hipMalloc((void **)&s->d_arrive, ncnt * sizeof(unsigned)));
-      const hipError_t e = hipMemsetAsync(s->d_arrive, 0, ncnt * sizeof(unsigned), stream());
-      if (e != hipSuccess) { (void)hipFree(s->d_arrive); s->d_arrive = nullptr; return hip_fail(e, "hipMemsetAsync(d_arrive)", __FILE__, __LINE__); }
-    }
-    if (!s->d_loop_sums) CUP3D_HIP(hipMalloc((void **)&s->d_loop_sums, 2 * sizeof(LoopSums)));
+    if (!s->d_arrive_sums && (rc = s->d_arrive_sums.alloc_zeroed(8 * (n1 + n2) + 8, stream(), s))) return rc;
+    if (!s->d_arrive && (rc = s->d_arrive.alloc_zeroed(ncnt, stream()))) { s->d_arrive.reset(); return rc; }  // never kept unzeroed
+    if (!s->d_loop_sums && (rc = s->d_loop_sums.alloc(2))) return rc;
     if (!s->h_early_fail_dev) {
-      if (!s->h_early_fail) CUP3D_HIP(hipHostMalloc((void **)&s->h_early_fail, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
+      if (!s->h_early_fail && (rc = s->h_early_fail.alloc(1, hipHostMallocMapped | hipHostMallocCoherent))) return rc;
       *s->h_early_fail = 0;
-      CUP3D_HIP(hipHostGetDevicePointer((void **)&s->h_early_fail_dev, s->h_early_fail, 0));
+      if ((rc = s->h_early_fail.device_alias(&s->h_early_fail_dev))) return rc;
     }
   }
-  if (!s->h_ctl_dev) {  // the solver's scalar struct (device) and the pinned ring its outcome reaches the host through: all three or none
-    hipError_t e = s->d_ctl ? hipSuccess : hipMalloc(&s->d_ctl, sizeof(SolverCtl));
-    if (e == hipSuccess && !s->h_ctl) {
-      e = hipHostMalloc(&s->h_ctl, 4 * sizeof(CtlSlot), hipHostMallocMapped | hipHostMallocCoherent);
-      if (e == hipSuccess) memset(s->h_ctl, 0, 4 * sizeof(CtlSlot));
+  if (!s->h_ctl_dev) {  // the solver's scalar struct (device) and the pinned ring its outcome reaches the host through; each guarded by itself
+    if (!s->d_ctl && (rc = s->d_ctl.alloc(sizeof(SolverCtl)))) return rc;
+    if (!s->h_ctl) {
+      if ((rc = s->h_ctl.alloc(4 * sizeof(CtlSlot), hipHostMallocMapped | hipHostMallocCoherent))) return rc;
+      memset(s->h_ctl, 0, 4 * sizeof(CtlSlot));
     }
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&s->h_ctl_dev, s->h_ctl, 0);
-    if (e != hipSuccess) {  // leave nothing half-built behind: the next solve starts over
-      if (s->d_ctl) (void)hipFree(s->d_ctl);
-      if (s->h_ctl) (void)hipHostFree(s->h_ctl);
-      s->d_ctl = s->h_ctl = s->h_ctl_dev = nullptr;
-      return hip_fail(e, "SolverCtl allocation", __FILE__, __LINE__);
-    }
+    if ((rc = s->h_ctl.device_alias(&s->h_ctl_dev))) return rc;
   }
   if (s->sv[0]) return CUP3D_OK;
-  for (int i = 0; i < NVEC; ++i) {
-    int rc = sim_alloc(&s->sv[i], (size_t)s->nvis * 512, s);  // nvis: the LHS reads ghost blocks of any of them on a rank view
-    if (rc) return rc;
-  }
+  for (int i = 0; i < NVEC; ++i)
+    if ((rc = s->sv[i].alloc_zeroed((size_t)s->nvis * 512, stream(), s))) return rc;  // nvis: the LHS reads ghost blocks of any of them on a rank view
   return CUP3D_OK;
 }
 
@@ -88,7 +71,7 @@ static int ensure_vectors(Sim *s) {
 
 // the host waits for the outcome of a fused iteration: slot seq & 3 of the pinned ring carries `seq` once the struct is in place
 static int wait_status(Sim *s, unsigned seq, SolverCtl *out) {
-  const CtlSlot *sl = reinterpret_cast<const CtlSlot *>(s->h_ctl) + (seq & 3);
+  const CtlSlot *sl = s->h_ctl.as<const CtlSlot>() + (seq & 3);
   const volatile unsigned *flag = &sl->seq;
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spin = 1; *flag != seq; ++spin) {
@@ -195,7 +178,7 @@ struct Solver {
     sums = want_sums ? s->d_partials + (size_t)s->max_groups * 8 : nullptr;
     cg_it = profile_on() ? cg_iters_buffer(s) : nullptr;
     gd = s->gdev();
-    d_ctl = reinterpret_cast<SolverCtl *>(s->d_ctl);
+    d_ctl = s->d_ctl.as<SolverCtl>();
     ring = reinterpret_cast<CtlSlot *>(s->h_ctl_dev);
     direct = red.direct();
     split = s->grid->nranks > 1;
@@ -604,18 +587,11 @@ struct Solver {
   int path_checksum(unsigned long long *sc) {
     if (!fuse) { set_error("cup3d_poisson_path_checksum: block_solver %d has no fused loop kernels (0, 1 and 2 do)", P.block_solver); return CUP3D_EINVAL; }
     TRY(early_setup());
-    int32_t *d_index = nullptr, *d_level = nullptr;  // the blocks' positions and levels, for k_selfcheck_fill
-    const size_t nidx = (size_t)s->nb * 3;
-    CUP3D_HIP(hipMalloc((void **)&d_index, nidx * sizeof(int32_t)));
-    hipError_t e = hipMemcpyAsync(d_index, s->grid->index.data(), nidx * sizeof(int32_t), hipMemcpyHostToDevice, stream());
-    if (e == hipSuccess && s->grid->multilevel) {
-      e = hipMalloc((void **)&d_level, (size_t)s->nb * sizeof(int32_t));
-      if (e == hipSuccess) e = hipMemcpyAsync(d_level, s->grid->blevel.data(), (size_t)s->nb * sizeof(int32_t), hipMemcpyHostToDevice, stream());
-    }
-    const int rc = e != hipSuccess ? hip_fail(e, "cup3d_poisson_path_checksum tables", __FILE__, __LINE__) : checksum_iteration(d_index, d_level, sc);
-    (void)hipStreamSynchronize(stream());
-    if (d_index) (void)hipFree(d_index);
-    if (d_level) (void)hipFree(d_level);
+    Dev<int32_t> d_index, d_level;  // the blocks' positions and levels, for k_selfcheck_fill
+    int rc = d_index.upload(s->grid->index.data(), (size_t)s->nb * 3, stream(), IfEmpty::null);
+    if (!rc && s->grid->multilevel) rc = d_level.upload(s->grid->blevel.data(), (size_t)s->nb, stream(), IfEmpty::null);
+    if (!rc) rc = checksum_iteration(d_index, d_level, sc);
+    (void)hipStreamSynchronize(stream());  // the tables are freed on return
     return rc;
   }
 };
@@ -681,16 +657,13 @@ int cup3d_debug_ctl_step(int step, double *io, const double *totals) {
 #ifdef CUP3D_TESTING  // test / tuning support: not in the release library at all
 int cup3d_debug_wave_sum(const double *in64, double *out128) {
   if (!in64 || !out128) return CUP3D_EINVAL;
-  double *d = nullptr;
-  CUP3D_HIP(hipMalloc((void **)&d, 192 * sizeof(double)));
-  hipError_t e = hipMemcpy(d, in64, 64 * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_debug_wave_sum, dim3(1), dim3(64), 0, stream(), d, d + 64);
-    e = hipStreamSynchronize(stream());
-    if (e == hipSuccess) e = hipMemcpy(out128, d + 64, 128 * sizeof(double), hipMemcpyDeviceToHost);
-  }
-  hipFree(d);
-  if (e != hipSuccess) return hip_fail(e, "cup3d_debug_wave_sum", __FILE__, __LINE__);
+  Dev<double> d;
+  int rc = d.alloc(192);
+  if (rc) return rc;
+  CUP3D_HIP(hipMemcpy(d, in64, 64 * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_debug_wave_sum, dim3(1), dim3(64), 0, stream(), d.get(), d + 64);
+  CUP3D_HIP(hipStreamSynchronize(stream()));
+  CUP3D_HIP(hipMemcpy(out128, d + 64, 128 * sizeof(double), hipMemcpyDeviceToHost));
   return CUP3D_OK;
 }
 
@@ -699,18 +672,15 @@ int cup3d_debug_cg_div(const double *n, const double *d, long count, double *out
   if (!n || !d || !out || count < 0 || count > (1L << 30)) return CUP3D_EINVAL;
   if (count == 0) return CUP3D_OK;
   const size_t bytes = (size_t)count * sizeof(double);
-  double *b = nullptr;
-  CUP3D_HIP(hipMalloc((void **)&b, 3 * bytes));
-  hipError_t e = hipMemcpy(b, n, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(b + count, d, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_debug_cg_div, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream(), b, b + count, count, b + 2 * count);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(stream());
-    if (e == hipSuccess) e = hipMemcpy(out, b + 2 * count, bytes, hipMemcpyDeviceToHost);
-  }
-  hipFree(b);
-  if (e != hipSuccess) return hip_fail(e, "cup3d_debug_cg_div", __FILE__, __LINE__);
+  Dev<double> b;
+  int rc = b.alloc(3 * (size_t)count);
+  if (rc) return rc;
+  CUP3D_HIP(hipMemcpy(b, n, bytes, hipMemcpyHostToDevice));
+  CUP3D_HIP(hipMemcpy(b + count, d, bytes, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_debug_cg_div, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream(), b.get(), b + count, count, b + 2 * count);
+  CUP3D_HIP(hipGetLastError());
+  CUP3D_HIP(hipStreamSynchronize(stream()));
+  CUP3D_HIP(hipMemcpy(out, b + 2 * count, bytes, hipMemcpyDeviceToHost));
   return CUP3D_OK;
 }
 

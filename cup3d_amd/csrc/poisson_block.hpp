@@ -454,7 +454,7 @@ static int fdm_setup() {
 }
 
 static int *cg_iters_buffer(Sim *s) {  // per-block CG iteration counts of the last launch (measurement only)
-  if (!s->d_cg_iters && hipMalloc((void **)&s->d_cg_iters, (size_t)s->nb * sizeof(int)) != hipSuccess) return nullptr;
+  if (!s->d_cg_iters && s->d_cg_iters.alloc((size_t)s->nb)) return nullptr;
   return s->d_cg_iters;
 }
 

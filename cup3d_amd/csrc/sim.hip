@@ -144,12 +144,6 @@ double *Sim::field(int id, int *ncomp) const {
   *ncomp = 0;
   return nullptr;
 }
-int sim_alloc(double **p, size_t n, Sim *s) {
-  CUP3D_HIP(hipMalloc((void **)p, n * sizeof(double)));
-  CUP3D_HIP(hipMemsetAsync(*p, 0, n * sizeof(double), g_stream));
-  s->bytes += n * sizeof(double);
-  return CUP3D_OK;
-}
 
 // ------------------------------------------------------------------ layout conversion
 // reference block memory [blk][cell][c]  <->  device slab [blk][c][cell]
@@ -340,24 +334,17 @@ static int sim_build(Sim *s, const Grid *g) {
   const size_t nb = (size_t)s->nb, nv = (size_t)s->nvis;
   const bool view = g->n_local >= 0;
   int rc;
-  auto up = [&](int32_t **d, const std::vector<int32_t> &v) -> int {
-    if (v.empty()) { *d = nullptr; return CUP3D_OK; }
-    CUP3D_HIP(hipMalloc((void **)d, v.size() * sizeof(int32_t)));
-    CUP3D_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    return CUP3D_OK;
-  };
-#define A(ptr, n) if ((rc = sim_alloc(&(ptr), (n), s)) != CUP3D_OK) return rc;
-  A(s->vel, nv * 1536) A(s->vel2, nv * 1536) A(s->tmpV, nv * 1536)
-  A(s->pres, nv * 512) A(s->lhs, nv * 512) A(s->chi, nv * 512) A(s->pold, nv * 512)
+  // index tables: a blocking copy, nothing (nullptr) for an empty one, not on the ledger; zeroed field arrays: on it
+  constexpr IfEmpty null = IfEmpty::null;
   s->max_groups = 4096;
-  A(s->d_partials, (size_t)s->max_groups * 8 + nb) A(s->d_red, kRedSize)
-  CUP3D_HIP(hipHostMalloc((void **)&s->h_red, 17 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));  // 16 totals + the sequence word of Reducer
+  if ((rc = s->vel.alloc_zeroed(nv * 1536, g_stream, s)) || (rc = s->vel2.alloc_zeroed(nv * 1536, g_stream, s)) || (rc = s->tmpV.alloc_zeroed(nv * 1536, g_stream, s)) || (rc = s->pres.alloc_zeroed(nv * 512, g_stream, s)) ||
+      (rc = s->lhs.alloc_zeroed(nv * 512, g_stream, s)) || (rc = s->chi.alloc_zeroed(nv * 512, g_stream, s)) || (rc = s->pold.alloc_zeroed(nv * 512, g_stream, s)) ||
+      (rc = s->d_partials.alloc_zeroed((size_t)s->max_groups * 8 + nb, g_stream, s)) || (rc = s->d_red.alloc_zeroed(kRedSize, g_stream, s)) ||
+      (rc = s->h_red.alloc(17, hipHostMallocMapped | hipHostMallocCoherent)))  // 16 totals + the sequence word of Reducer
+    return rc;
   memset(s->h_red, 0, 17 * sizeof(double));
-  CUP3D_HIP(hipHostGetDevicePointer((void **)&s->h_red_dev, s->h_red, 0));
-  CUP3D_HIP(hipMalloc((void **)&s->d_counters, 4 * sizeof(unsigned)));
-  CUP3D_HIP(hipMemsetAsync(s->d_counters, 0, 4 * sizeof(unsigned), g_stream));
-  if ((rc = up(&s->d_nbr, g->nbr))) return rc;
-  if (g->nranks > 1 && ((rc = up(&s->d_inner, g->inner)) || (rc = up(&s->d_boundary, g->boundary)) || (rc = up(&s->d_send_faces, g->send_faces)))) return rc;
+  if ((rc = s->h_red.device_alias(&s->h_red_dev)) || (rc = s->d_counters.alloc_zeroed(4, g_stream)) || (rc = s->d_nbr.upload(g->nbr, null))) return rc;
+  if (g->nranks > 1 && ((rc = s->d_inner.upload(g->inner, null)) || (rc = s->d_boundary.upload(g->boundary, null)) || (rc = s->d_send_faces.upload(g->send_faces, null)))) return rc;
   if (g->nranks > 1 || debug_option("force_allreduce")) {  // ("force_allreduce", testing build: ONE rank whose scalars go through the communicator -- latency measurements)
     // the communication stream outranks the compute stream: its pack kernels, RCCL's send / receive kernels and the one-thread
     // recurrence steps are dispatched ahead of the tens of thousands of loop-kernel workgroups queued on the compute stream, so an
@@ -368,8 +355,8 @@ static int sim_build(Sim *s, const Grid *g) {
   }
   if (g->nranks > 1 && !g->multilevel) {
     const size_t slab = 3 * 3 * 64;  // widest exchange: 3 components x 3 layers
-    if (g->n_recv_faces) A(s->halo_recv, (size_t)g->n_recv_faces * slab)
-    if (!g->send_faces.empty()) A(s->halo_send, g->send_faces.size() * slab)
+    if (g->n_recv_faces && (rc = s->halo_recv.alloc_zeroed((size_t)g->n_recv_faces * slab, g_stream, s))) return rc;
+    if (!g->send_faces.empty() && (rc = s->halo_send.alloc_zeroed(g->send_faces.size() * slab, g_stream, s))) return rc;
   }
   if (g->multilevel) {
     // ghost slabs are produced for the LOCAL interface faces only (a view also lists the fine faces of ghost blocks, whose
@@ -386,9 +373,9 @@ static int sim_build(Sim *s, const Grid *g) {
     }
     s->n_restrict = (unsigned)lr.size();
     s->n_prolong = (unsigned)lp.size();
-    if ((rc = up(&s->d_amr_faces, g->amr_faces)) || (rc = up(&s->d_amr_fine, g->amr_fine)) || (rc = up(&s->d_nbr27, g->nbr27)) ||
-        (rc = up(&s->d_index, g->index)) || (rc = up(&s->d_restrict_list, lr)) || (rc = up(&s->d_prolong_list, lp)) ||
-        (rc = up(&s->d_fix_list[0], g->fix_faces[0])) || (rc = up(&s->d_fix_list[1], g->fix_faces[1])) || (rc = up(&s->d_fix_list[2], g->fix_faces[2])))
+    if ((rc = s->d_amr_faces.upload(g->amr_faces, null)) || (rc = s->d_amr_fine.upload(g->amr_fine, null)) || (rc = s->d_nbr27.upload(g->nbr27, null)) ||
+        (rc = s->d_index.upload(g->index, null)) || (rc = s->d_restrict_list.upload(lr, null)) || (rc = s->d_prolong_list.upload(lp, null)) ||
+        (rc = s->d_fix_list[0].upload(g->fix_faces[0], null)) || (rc = s->d_fix_list[1].upload(g->fix_faces[1], null)) || (rc = s->d_fix_list[2].upload(g->fix_faces[2], null)))
       return rc;
     {  // the corrected faces grouped by block (k_flux_fix_blocks): blocks in slot order, faces x-, x+, y-, y+, z-, z+
       std::vector<int32_t> of_slot((size_t)std::max<int64_t>(nv, 1), -1), tab;
@@ -399,9 +386,9 @@ static int sim_build(Sim *s, const Grid *g) {
           tab[(size_t)of_slot[(size_t)slot] * 6 + f] = e;
         }
       s->n_fix_blocks = (unsigned)(tab.size() / 6);
-      if ((rc = up(&s->d_fix_blocks, tab))) return rc;
+      if ((rc = s->d_fix_blocks.upload(tab, null))) return rc;
     }
-    A(s->d_hb, nv)
+    if ((rc = s->d_hb.alloc_zeroed(nv, g_stream, s))) return rc;
     CUP3D_HIP(hipMemcpy(s->d_hb, g->hb.data(), nv * sizeof(double), hipMemcpyHostToDevice));
     {
       std::vector<unsigned char> mask(std::max<size_t>(nb, 1), 0);
@@ -410,9 +397,7 @@ static int sim_build(Sim *s, const Grid *g) {
         if (g->amr_faces[2 * e + 1] == 1) mask[(size_t)(g->amr_faces[2 * e] / 6)] = 1;
       for (size_t b = 0; b < nb; ++b) if (mask[b]) raw.push_back((int32_t)b);
       s->n_raw = (unsigned)raw.size();
-      CUP3D_HIP(hipMalloc((void **)&s->d_raw_mask, mask.size()));
-      CUP3D_HIP(hipMemcpy(s->d_raw_mask, mask.data(), mask.size(), hipMemcpyHostToDevice));
-      if ((rc = up(&s->d_raw_list, raw))) return rc;
+      if ((rc = s->d_raw_mask.upload(mask, IfEmpty::null)) || (rc = s->d_raw_list.upload(raw, null))) return rc;
     }
     if (!view) {  // one rank: which blocks have an interface face, which have none
       std::vector<int32_t> iface, plain;
@@ -424,38 +409,33 @@ static int sim_build(Sim *s, const Grid *g) {
       }
       s->n_iface = (unsigned)iface.size();
       s->n_plain = (unsigned)plain.size();
-      if ((rc = up(&s->d_iface_list, iface)) || (rc = up(&s->d_plain_list, plain))) return rc;
+      if ((rc = s->d_iface_list.upload(iface, null)) || (rc = s->d_plain_list.upload(plain, null))) return rc;
     }
     const size_t ne = (size_t)std::max<int64_t>(g->n_amr_faces(), 1);
     // ghost slabs: widest use = 3 components x 3 layers; the pressure RHS keeps a second set (udef) behind the first
-    A(s->halo_recv, ne * 9 * 64)
-    A(s->d_flux, ne * 3 * 64)
+    if ((rc = s->halo_recv.alloc_zeroed(ne * 9 * 64, g_stream, s)) || (rc = s->d_flux.alloc_zeroed(ne * 3 * 64, g_stream, s))) return rc;
     if (view) {
-      if ((rc = up(&s->d_send_blocks, g->send_blocks)) || (rc = up(&s->d_send_flux, g->send_flux_faces))) return rc;
+      if ((rc = s->d_send_blocks.upload(g->send_blocks, null)) || (rc = s->d_send_flux.upload(g->send_flux_faces, null))) return rc;
       const size_t need = std::max(g->send_blocks.size() * 1536, g->send_flux_faces.size() * 3 * 64);
-      if (need) A(s->halo_send, need)
+      if (need && (rc = s->halo_send.alloc_zeroed(need, g_stream, s))) return rc;
       // sub-box form of the ghost-block exchange: boxes + packed-message offsets of both width classes, one staging buffer
       size_t most = 0;
       for (int k = 0; k < 2 && !g->send_cells[k].empty(); ++k) {
-        auto upload = [&](const std::vector<uint8_t> &box, unsigned char **d_box, long long **d_off, size_t *total) -> int {
+        auto upload = [&](const std::vector<uint8_t> &box, Dev<unsigned char> &d_box, Dev<long long> &d_off, size_t *total) -> int {
           std::vector<long long> off(box.size() / 6 + 1, 0);
           for (size_t i = 0; i < box.size() / 6; ++i)
             off[i + 1] = off[i] + (long long)(box[6 * i + 3] - box[6 * i]) * (box[6 * i + 4] - box[6 * i + 1]) * (box[6 * i + 5] - box[6 * i + 2]);
           *total = (size_t)off.back();
-          CUP3D_HIP(hipMalloc((void **)d_box, std::max<size_t>(box.size(), 1)));
-          CUP3D_HIP(hipMalloc((void **)d_off, off.size() * sizeof(long long)));
-          if (!box.empty()) CUP3D_HIP(hipMemcpy(*d_box, box.data(), box.size(), hipMemcpyHostToDevice));
-          CUP3D_HIP(hipMemcpy(*d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
-          return CUP3D_OK;
+          int rc2 = d_box.upload(box, IfEmpty::one);
+          return rc2 ? rc2 : d_off.upload(off, IfEmpty::one);
         };
         size_t ts = 0, tr = 0;
-        if ((rc = upload(g->send_box[k], &s->d_send_box[k], &s->d_send_off[k], &ts)) || (rc = upload(g->ghost_box[k], &s->d_ghost_box[k], &s->d_ghost_off[k], &tr))) return rc;
+        if ((rc = upload(g->send_box[k], s->d_send_box[k], s->d_send_off[k], &ts)) || (rc = upload(g->ghost_box[k], s->d_ghost_box[k], s->d_ghost_off[k], &tr))) return rc;
         most = std::max(most, tr);
       }
-      if (most) A(s->box_recv, most * 3)
+      if (most && (rc = s->box_recv.alloc_zeroed(most * 3, g_stream, s))) return rc;
     }
   }
-#undef A
   CUP3D_HIP(hipEventCreateWithFlags(&s->ev_a, hipEventDisableTiming));
   CUP3D_HIP(hipEventCreateWithFlags(&s->ev_b, hipEventDisableTiming));
   CUP3D_HIP(hipEventCreateWithFlags(&s->ev_h1, hipEventDisableTiming));
@@ -480,14 +460,8 @@ Sim *sim_comm_only(const Grid *g, hipStream_t comm_stream) {
   s->grid = g;
   s->nb = s->nvis = g->nblocks();
   s->comm_stream = comm_stream;
-  bool ok = true;
-  auto up = [&](int32_t **d, const std::vector<int32_t> &v) {
-    if (v.empty()) return;
-    ok = ok && hipMalloc((void **)d, v.size() * sizeof(int32_t)) == hipSuccess && hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-  };
-  up(&s->d_send_faces, g->send_faces);
-  if (g->n_recv_faces) ok = ok && hipMalloc((void **)&s->halo_recv, (size_t)g->n_recv_faces * 64 * sizeof(double)) == hipSuccess;
-  if (!g->send_faces.empty()) ok = ok && hipMalloc((void **)&s->halo_send, g->send_faces.size() * 64 * sizeof(double)) == hipSuccess;
+  bool ok = s->d_send_faces.upload(g->send_faces, IfEmpty::null) == CUP3D_OK && s->halo_recv.alloc((size_t)g->n_recv_faces * 64) == CUP3D_OK &&
+            s->halo_send.alloc(g->send_faces.size() * 64) == CUP3D_OK;
   hipEvent_t *ev[] = {&s->ev_h1, &s->ev_h2, &s->ev_vc_pack, &s->ev_vc_done};
   for (hipEvent_t *e : ev) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
   if (!ok) { sim_comm_only_destroy(s); return nullptr; }
@@ -496,9 +470,6 @@ Sim *sim_comm_only(const Grid *g, hipStream_t comm_stream) {
 void sim_comm_only_destroy(Sim *s) {
   if (!s) return;
   vcomm_unregister(s);
-  if (s->d_send_faces) hipFree(s->d_send_faces);
-  if (s->halo_recv) hipFree(s->halo_recv);
-  if (s->halo_send) hipFree(s->halo_send);
   hipEvent_t ev[] = {s->ev_h1, s->ev_h2, s->ev_vc_pack, s->ev_vc_done};
   for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
   delete s;  // the communication stream belongs to the finest level's Sim
@@ -524,7 +495,6 @@ int cup3d_sim_create(const cup3d_grid_t *gh, cup3d_sim_t **out) {
   return CUP3D_OK;
 }
 
-static void release_stage(Sim *s);
 void cup3d_sim_destroy(cup3d_sim_t *h) {
   if (!h) return;
   Sim *s = reinterpret_cast<Sim *>(h);
@@ -534,38 +504,10 @@ void cup3d_sim_destroy(cup3d_sim_t *h) {
   labs_destroy(s);
   forces_destroy(s);
   retained_destroy(s);
-  double *ptrs[] = {s->vel, s->vel2, s->tmpV, s->pres, s->lhs, s->chi, s->pold, s->d_partials, s->d_red, s->halo_recv, s->halo_send, s->d_block_dots,
-                    s->d_hb, s->d_flux};
-  for (double *p : ptrs) if (p) hipFree(p);
-  for (double *p : s->sv) if (p) hipFree(p);
-  if (s->h_red) hipHostFree(s->h_red);
-  if (s->d_ctl) hipFree(s->d_ctl);
-  if (s->h_ctl) hipHostFree(s->h_ctl);
-  if (s->d_counters) hipFree(s->d_counters);
-  if (s->d_cg_iters) hipFree(s->d_cg_iters);
-  if (s->d_arrive_sums) hipFree(s->d_arrive_sums);
-  if (s->d_arrive) hipFree(s->d_arrive);
-  if (s->d_loop_sums) hipFree(s->d_loop_sums);
-  if (s->h_early_fail) hipHostFree(s->h_early_fail);
-  release_stage(s);
-  int32_t *ip[] = {s->d_nbr, s->d_inner, s->d_boundary, s->d_send_faces, s->d_amr_faces, s->d_amr_fine, s->d_nbr27, s->d_index,
-                   s->d_restrict_list, s->d_prolong_list, s->d_fix_list[0], s->d_fix_list[1], s->d_fix_list[2], s->d_fix_blocks, s->d_send_blocks, s->d_send_flux, s->d_raw_list, s->d_iface_list, s->d_plain_list};
-  if (s->d_raw_mask) hipFree(s->d_raw_mask);
-  for (int k = 0; k < 2; ++k) {
-    void *bp[] = {s->d_send_box[k], s->d_ghost_box[k], s->d_send_off[k], s->d_ghost_off[k]};
-    for (void *p : bp) if (p) hipFree(p);
-  }
-  if (s->box_recv) hipFree(s->box_recv);
-  for (int32_t *p : ip) if (p) hipFree(p);
   if (s->comm_stream) hipStreamDestroy(s->comm_stream);
-  if (s->ev_a) hipEventDestroy(s->ev_a);
-  if (s->ev_b) hipEventDestroy(s->ev_b);
-  if (s->ev_h1) hipEventDestroy(s->ev_h1);
-  if (s->ev_h2) hipEventDestroy(s->ev_h2);
-  if (s->ev_m) hipEventDestroy(s->ev_m);
-  if (s->ev_vc_pack) hipEventDestroy(s->ev_vc_pack);
-  if (s->ev_vc_done) hipEventDestroy(s->ev_vc_done);
-  delete s;
+  for (hipEvent_t e : {s->ev_stage[0], s->ev_stage[1], s->ev_a, s->ev_b, s->ev_h1, s->ev_h2, s->ev_m, s->ev_vc_pack, s->ev_vc_done})
+    if (e) hipEventDestroy(e);
+  delete s;  // every buffer goes with its owner member
 }
 size_t cup3d_sim_device_bytes(const cup3d_sim_t *h) { return h ? reinterpret_cast<const Sim *>(h)->bytes : 0; }
 
@@ -628,30 +570,20 @@ int cup3d_sim_download(cup3d_sim_t *h, int field, double *blocks) {
 //   * the gather / scatter runs on up to 16 host threads (more were slower on the two-socket GPU host) (a single core copies ~10 GB/s, PCIe Gen5 x16 carries ~55);
 //   * two pinned staging buffers and two device staging buffers alternate, so that the host works on chunk k+1 while chunk k is on
 //     the bus and in the layout kernel (events, no stream synchronisation inside the loop).
-static void release_stage(Sim *s) {
-  if (s->h_stage) hipHostFree(s->h_stage);
-  if (s->d_stage) hipFree(s->d_stage);
-  if (s->h_stage_slots) hipHostFree(s->h_stage_slots);
-  if (s->d_stage_slots) hipFree(s->d_stage_slots);
-  for (hipEvent_t &e : s->ev_stage) { if (e) hipEventDestroy(e); e = nullptr; }
-  s->h_stage = s->d_stage = nullptr;
-  s->h_stage_slots = s->d_stage_slots = nullptr;
-}
 static int ensure_stage(Sim *s) {
   if (s->stage_ready) return CUP3D_OK;
   // per buffer: at most 16384 vector blocks (192 MiB), never more than the sim holds -- a 64-block test sim pins 1.5 MiB, not 400
   s->stage_blocks = (size_t)std::min<int64_t>(16384, std::max<int64_t>(s->nb, 1));
   const size_t nd = 2 * s->stage_blocks * 1536;
-  hipError_t e = hipHostMalloc((void **)&s->h_stage, nd * sizeof(double), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc((void **)&s->d_stage, nd * sizeof(double));
-  if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_stage_slots, s->stage_blocks * sizeof(int32_t), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc((void **)&s->d_stage_slots, s->stage_blocks * sizeof(int32_t));
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&s->ev_stage[i], hipEventDisableTiming);
-  if (e != hipSuccess) {  // all or nothing: a later call must not find half a staging area
-    release_stage(s);
-    return hip_fail(e, "ensure_stage", __FILE__, __LINE__);
-  }
-  s->bytes += nd * sizeof(double) + s->stage_blocks * sizeof(int32_t);  // the device half (the pinned host half is as large)
+  // a call that fails half way leaves what it made to the Sim; the next one makes the rest.  The device half is on the ledger (the
+  // pinned host half is as large)
+  int rc;
+  if ((!s->h_stage && (rc = s->h_stage.alloc(nd, hipHostMallocDefault))) || (!s->d_stage && (rc = s->d_stage.alloc(nd, s))) ||
+      (!s->h_stage_slots && (rc = s->h_stage_slots.alloc(s->stage_blocks, hipHostMallocDefault))) ||
+      (!s->d_stage_slots && (rc = s->d_stage_slots.alloc(s->stage_blocks, s))))
+    return rc;
+  for (hipEvent_t &e : s->ev_stage)
+    if (!e) CUP3D_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   s->stage_ready = true;
   return CUP3D_OK;
 }

@@ -6,6 +6,7 @@
 // cells are never materialised in HBM: kernels stage the ghosted tile of a block in
 // LDS straight from the neighbour slots (this replaces BlockLab::load, 3623-3743).
 // Face slabs owned by other ranks live in `halo_*` buffers filled by RCCL.
+// Every buffer is an owner member (devmem.hpp): it goes with its Sim, and what is not listed anywhere cannot be forgotten there.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,15 +21,9 @@
 #endif
 #include "grid.hpp"
 
-namespace cup3d {
+#include "devmem.hpp"  // set_error, CUP3D_HIP; Dev<T>, DevGrow, Pinned<T>: every buffer below is owned by type and goes with its Sim
 
-void set_error(const char *fmt, ...);
-int hip_fail(hipError_t e, const char *what, const char *file, int line);
-#define CUP3D_HIP(call)                                                        \
-  do {                                                                         \
-    hipError_t e_ = (call);                                                    \
-    if (e_ != hipSuccess) return ::cup3d::hip_fail(e_, #call, __FILE__, __LINE__); \
-  } while (0)
+namespace cup3d {
 
 hipStream_t stream();  // compute stream (cup3d_set_stream)
 // Two flavours of the library are built from these sources (Makefile): libcup3d_hip.so, the release build, and
@@ -101,11 +96,11 @@ struct Sim {
   int64_t nb = 0;    // local blocks: what the kernels sweep and what crosses the host boundary
   int64_t nvis = 0;  // block slots of every field array: nb + the ghost blocks of a rank view (Grid::rank_view), else nb
   // topology on device
-  int32_t *d_nbr = nullptr, *d_inner = nullptr, *d_boundary = nullptr, *d_send_faces = nullptr;
+  Dev<int32_t> d_nbr, d_inner, d_boundary, d_send_faces;
   // fields
-  double *vel = nullptr, *vel2 = nullptr, *tmpV = nullptr;    // [nb][3][512]
-  double *pres = nullptr, *lhs = nullptr, *chi = nullptr;     // [nb][512]
-  double *pold = nullptr;
+  Dev<double> vel, vel2, tmpV;    // [nb][3][512]
+  Dev<double> pres, lhs, chi;     // [nb][512]
+  Dev<double> pold;
   bool chi_nonzero = false;   // chi was uploaded / filled non-zero: the pressure RHS reads chi and udef (= tmpV)
   bool udef_nonzero = false;  // tmpV holds the udef of the NEXT projection (uploaded, filled or cup3d_update_tmpv since the last one)
   // cup3d_sim_set_obstacles: does ANY rank hold an obstacle (the reference's obstacle_vector is replicated, every rank knows)?
@@ -119,22 +114,23 @@ struct Sim {
   int block_solver = 0;  // cup3d_poisson_params.block_solver of the running solve
   int scalar_bc_dir = -1;  // >= 0 while a Helmholtz solve of the implicit diffusion runs: domain-face rule of the scalar tiles
   // solver vectors (allocated on first solve), each [nb][512]
-  double *sv[18] = {nullptr};
+  Dev<double> sv[18];
   // reductions
-  double *d_partials = nullptr;  // [max_groups][8]
-  double *d_red = nullptr;       // [kRedSize] final reduced scalars, see RedSlot
+  Dev<double> d_partials;  // [max_groups][8]
+  Dev<double> d_red;       // [kRedSize] final reduced scalars, see RedSlot
   const double *sums_of = nullptr;  // vector whose per-block sums (mean constraint) are current in d_partials' tail
-  double *h_red = nullptr;       // pinned host mirror
+  Pinned<double> h_red;       // pinned host mirror
   double *h_red_dev = nullptr;   // the same memory as the device sees it (kernels store the reduced scalars there directly)
-  unsigned *d_counters = nullptr;  // [4] tickets of grid_sum_finish (tile.hpp), zero between launches
-  int *d_cg_iters = nullptr;       // [nb] CG iterations per block of the last block-CG launch (only while profiling)
-  double *d_block_dots = nullptr;  // [7][nb] per-block dot products of the fused loop + block-CG kernels (poisson.hip)
+  Dev<unsigned> d_counters;  // [4] tickets of grid_sum_finish (tile.hpp), zero between launches
+  Dev<int> d_cg_iters;       // [nb] CG iterations per block of the last block-CG launch (only while profiling)
+  Dev<double> d_block_dots;  // [7][nb] per-block dot products of the fused loop + block-CG kernels (poisson.hip)
   // ... and what totals them inside those kernels (Arrive, poisson.hip): group / super-group sums, arrival counters, the two flags the
   // communication stream (dots) and the corner block's wavefront (mean-constraint total) wait for when the all-reduce starts early
-  double *d_arrive_sums = nullptr;
-  unsigned *d_arrive = nullptr;
-  struct LoopSums *d_loop_sums = nullptr;  // [2] (poisson.hip)
-  unsigned *h_early_fail = nullptr, *h_early_fail_dev = nullptr;  // pinned: a bounded device-side wait of the early all-reduce gave up
+  Dev<double> d_arrive_sums;
+  Dev<unsigned> d_arrive;
+  Dev<struct LoopSums> d_loop_sums;  // [2] (poisson.hip)
+  Pinned<unsigned> h_early_fail;
+  unsigned *h_early_fail_dev = nullptr;  // pinned: a bounded device-side wait of the early all-reduce gave up
   void *mg = nullptr;              // level hierarchy of the multigrid preconditioner (multigrid.hip), built on first use
   struct LabTables *labs = nullptr;  // tables and staging buffer of cup3d_sim_labs (amr.hip), built on first use
   struct LabsView *labs_view = nullptr;  // cup3d_sim_labs_over_ranks: the rank's tensorial view, its tables, the ghost pool (amr.hip)
@@ -145,43 +141,46 @@ struct Sim {
   struct RetainedObstacles *retained = nullptr;
   int max_groups = 0;
   // staging for host transfers
-  double *d_stage = nullptr;
-  double *h_stage = nullptr;  // pinned; two buffers of stage_blocks vector blocks each, like d_stage
+  Dev<double> d_stage;
+  Pinned<double> h_stage;  // pinned; two buffers of stage_blocks vector blocks each, like d_stage
   hipEvent_t ev_stage[2] = {nullptr, nullptr};
   size_t stage_blocks = 0;
-  bool stage_ready = false;  // every staging resource exists (ensure_stage is all-or-nothing)
-  int32_t *d_stage_slots = nullptr, *h_stage_slots = nullptr;  // block lists of the partial transfers (cup3d_sim_*_block_list)
+  bool stage_ready = false;  // every staging resource exists (a failed ensure_stage keeps what it made; the next call makes the rest)
+  Dev<int32_t> d_stage_slots;
+  Pinned<int32_t> h_stage_slots;  // block lists of the partial transfers (cup3d_sim_*_block_list)
   // multi-level mesh tables (amr.hip); all nullptr / 0 on uniform grids
-  int32_t *d_amr_faces = nullptr, *d_amr_fine = nullptr, *d_nbr27 = nullptr, *d_index = nullptr;
-  int32_t *d_restrict_list = nullptr, *d_prolong_list = nullptr, *d_fix_list[3] = {nullptr, nullptr, nullptr};
+  Dev<int32_t> d_amr_faces, d_amr_fine, d_nbr27, d_index;
+  Dev<int32_t> d_restrict_list, d_prolong_list, d_fix_list[3];
   const double *mean_total_of = nullptr, *mean_total = nullptr;  // the vector whose sum(p h^3) total is already in *mean_total (device)
   unsigned red_seq = 0;  // last sequence number handed to a reduction kernel (Reducer, poisson.hip)
   // BiCGSTAB's scalar recurrences on the device (SolverCtl, poisson.hip): the struct, and the pinned ring its outcome reaches the host through
-  void *d_ctl = nullptr, *h_ctl = nullptr, *h_ctl_dev = nullptr;
+  Dev<void> d_ctl;
+  Pinned<void> h_ctl;
+  void *h_ctl_dev = nullptr;
   unsigned ctl_seq = 0;
   unsigned n_restrict = 0, n_prolong = 0;
-  int32_t *d_fix_blocks = nullptr;  // [n_fix_blocks][6]: per block with a corrected (coarse-side) face, the interface face behind each of its six faces or -1
+  Dev<int32_t> d_fix_blocks;  // [n_fix_blocks][6]: per block with a corrected (coarse-side) face, the interface face behind each of its six faces or -1
   unsigned n_fix_blocks = 0;
   unsigned n_restrict_inner = 0, n_prolong_inner = 0;  // leading entries of the two lists that belong to inner blocks (rank views)
   struct { const double *field = nullptr; int nc = 0, w = 0, bc_dir = -1; double *slabs = nullptr; bool open = false; } pending_fill;  // halo_begin -> halo_finish
-  int32_t *d_send_blocks = nullptr, *d_send_flux = nullptr;  // rank views: exchange plans (comm.hip)
+  Dev<int32_t> d_send_blocks, d_send_flux;  // rank views: exchange plans (comm.hip)
   // ... and the sub-box form of the ghost-block exchange (Grid::ghost_box / send_box), per stencil-width class: boxes, the offset (in cells
   // per component) of every block's cells in the packed message, the staging buffer the messages arrive in before they are scattered
-  unsigned char *d_send_box[2] = {nullptr, nullptr}, *d_ghost_box[2] = {nullptr, nullptr};
-  long long *d_send_off[2] = {nullptr, nullptr}, *d_ghost_off[2] = {nullptr, nullptr};
-  double *box_recv = nullptr;
-  unsigned char *d_raw_mask = nullptr;  // [nb], see GridDev::raw
-  int32_t *d_raw_list = nullptr;        // the blocks with raw_mask set
+  Dev<unsigned char> d_send_box[2], d_ghost_box[2];
+  Dev<long long> d_send_off[2], d_ghost_off[2];
+  Dev<double> box_recv;
+  Dev<unsigned char> d_raw_mask;  // [nb], see GridDev::raw
+  Dev<int32_t> d_raw_list;        // the blocks with raw_mask set
   // multi-level mesh on one rank: blocks with an interface face (coarse/fine: ghost slabs, face fluxes, flux correction) and the rest,
   // whose six faces are same-level blocks or domain faces -- for those the LHS application lives inside the fused loop kernels (poisson.hip)
-  int32_t *d_iface_list = nullptr, *d_plain_list = nullptr;
+  Dev<int32_t> d_iface_list, d_plain_list;
   unsigned n_iface = 0, n_plain = 0;
   bool corner_is_plain = false;  // the block of the mean-constraint row (grid->corner_slot) is in the plain list
   unsigned n_raw = 0;
-  double *d_hb = nullptr, *d_flux = nullptr;
+  Dev<double> d_hb, d_flux;
   // halo buffers (multi-rank)
-  double *halo_recv = nullptr, *halo_send = nullptr;  // n faces x 3 comps x 3 layers x 64
-  size_t bytes = 0;
+  Dev<double> halo_recv, halo_send;  // n faces x 3 comps x 3 layers x 64
+  size_t bytes = 0;  // cup3d_sim_device_bytes: what the allocations that name this Sim as `charge` hold (devmem.hpp)
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_h1 = nullptr, ev_h2 = nullptr, ev_m = nullptr;
   hipEvent_t ev_vc_pack = nullptr, ev_vc_done = nullptr;  // virtual communicator (tests): "my send buffer is packed" / "my copies are enqueued"
@@ -191,7 +190,7 @@ struct Sim {
   double *field(int id, int *ncomp) const;
 };
 
-int sim_alloc(double **p, size_t n_doubles, Sim *s);
+inline size_t &ledger(Sim *s) { return s->bytes; }
 // wrapping 64-bit sum of the bit patterns of n doubles (independent of launch geometry and of the sharding); synchronises
 int checksum_array(Sim *s, const double *p, long n, unsigned long long *sum);
 Sim *sim_comm_only(const Grid *g, hipStream_t comm_stream);  // exchange-only Sim of a coarse multigrid level (sim.hip)

@@ -142,6 +142,26 @@ def test_a_new_set_replaces_the_plan():
     assert lib().cup3d_update_tmpv_resident(resident.handle, 3) == ESTATE
 
 
+def test_a_one_block_obstacle_counts_by_the_formulas():
+    """one listed block: its slot list and the plan's three row tables are ONE int32 each, and are counted as 4 bytes -- the 8 bytes an
+    empty table gets are for an empty table only.  Over ranks an obstacle with a single local block is ordinary."""
+    c, o = K.CC.case("uniform8"), K.obstacles("uniform8")["A"]
+    i = int(np.argmax(o["chi"].reshape(len(o["ids"]), -1).sum(axis=1)))   # the block that holds most of the sphere
+    sim = cu.SimulationData(**c.sim_kwargs)
+    sim.upload("vel", RC.vel_of("uniform8"))
+    sim.lambda_penal, sim.bImplicitPenalization, sim.resident_obstacles = RC.LAMBDA, False, True
+    sim.shapes, sim.obstacles = [cu.ObstacleShape(o["ids"][i:i + 1], o["sdf"][i:i + 1], o["udef"][i:i + 1], o["transvel_correction"])], []
+    bytes0 = sim.device_bytes()
+    cu.CreateObstacles(sim)(0.0)
+    assert sim.device_bytes() - bytes0 == 24420   # slots 4 + geom 32 + sdf 8000 + chi 4096 + udef 12288, as per block in the tests above
+    sim.obstacles = [sim.shapes[0].data(K.APPROACH["A"]["vel"], K.APPROACH["A"]["omega"])]
+    bytes1 = sim.device_bytes()
+    cu.UpdateObstacles(sim)(RC.DT)
+    assert sim.device_bytes() - bytes1 == RC.plan_bytes([sim.shapes[0].slots]) == (32 + 72) + (3 * 4 + 29 * 8) + 2 * 4
+    del sim
+    gc.collect()
+
+
 def test_a_sim_with_a_plan_is_destroyed():
     c = K.CC.case("uniform8")
     sim = cu.SimulationData(**c.sim_kwargs)

@@ -146,6 +146,32 @@ struct Solver {
   const double *what_total;
   bool first_after_host;  // the next fused iteration follows a host-driven LHS(WHAT, T_): its total is complete before the launch
 
+  // what cup3d_debug_solver_state reports besides the scalars (test builds; nothing in the release build): q.y, y.y of the last
+  // iteration where the host saw them (host-driven iterations: the fused ones step omega on the device and the second loop's totals
+  // take their place in d_red), and the iteration count at the last restart
+#ifdef CUP3D_TESTING
+  double dbg_qy[2] = {NAN, NAN};
+  int dbg_restart_iter = -1;
+  void dbg_first_totals(const double *t) { dbg_qy[0] = t ? t[0] : NAN; dbg_qy[1] = t ? t[1] : NAN; }
+  void dbg_restarted() { dbg_restart_iter = hs.iter; }
+  int dbg_save() {
+    auto &D = s->dbg_solver;
+    const double io[16] = {hs.alpha, hs.beta, hs.omega, hs.r0r_prev, hs.norm, hs.init_norm, hs.min_norm, hs.tol, hs.tol_rel, (double)hs.state,
+                           (double)hs.restarts, (double)hs.max_restarts, (double)hs.xcur, (double)hs.xopt, (double)hs.iter,
+                           hs.iter > 0 && dbg_restart_iter == hs.iter ? 1.0 : 0.0};
+    memcpy(D.io, io, sizeof io);
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    CUP3D_HIP(hipMemcpy(D.totals, s->d_red + kRedDots, 7 * sizeof(double), hipMemcpyDeviceToHost));
+    D.totals[7] = dbg_qy[0]; D.totals[8] = dbg_qy[1];
+    D.valid = !helm;
+    return CUP3D_OK;
+  }
+#else
+  void dbg_first_totals(const double *) {}
+  void dbg_restarted() {}
+  int dbg_save() { return CUP3D_OK; }
+#endif
+
   Solver(Sim *sim, const cup3d_poisson_params &params, const HelmholtzOp *op, bool path_checksum_mode)
       : s(sim), P(params), helm(op), checksum(path_checksum_mode), red{sim} {}
 
@@ -282,6 +308,7 @@ struct Solver {
     hs.state = kRun;
     what_total = s->d_red + kRedMeanLhs;
     first_after_host = true;
+    dbg_restarted();
     return CUP3D_OK;
   }
 
@@ -302,6 +329,7 @@ struct Solver {
     TRY(PRE(Z_, ZHAT));        // overlapped with the reduction read-back, 14488-14489
     TRY(LHS(ZHAT, V_));
     TRY(red.wait());
+    dbg_first_totals(s->h_red);
     ctl_step1(hs, s->h_red);   // 14493
     if (k % 50 != 0) {
       ProfileScope ps("bicgstab_loop2");
@@ -368,6 +396,7 @@ struct Solver {
     if (want_sums) { s->mean_total_of = V.v[ZHAT]; s->mean_total = tot; }
     TRY(LHS(ZHAT, V_));                    // v = A zhat, 14489
     TRY(red.wait());
+    dbg_first_totals(s->h_red);
     ctl_step1(hs, s->h_red);               // 14493
     { ProfileScope ps("bicgstab_vector"); hipLaunchKernelGGL(k_refresh_pointwise<1>, GG, dim3(256), 0, stream(), g, V, hs.alpha, hs.omega, sums); }  // x, 14518
     if (want_sums) TRY(launch_mean_total(s));
@@ -529,6 +558,7 @@ struct Solver {
         }
         if (k == enq) break;  // nothing in flight: a host iteration is next, or the cap is reached
         TRY(wait_status(s, seq_of[k & 1], &hs));
+        dbg_first_totals(nullptr);
         ++k;
         if (hs.state == kDone) break;
         if (hs.state == kRestart) {  // what was enqueued ahead returned at once (state != kRun on the device)
@@ -555,7 +585,7 @@ struct Solver {
       res->norm = hs.norm;
       res->used_xopt = use_xopt;
     }
-    return CUP3D_OK;
+    return dbg_save();
   }
 
   // cup3d_poisson_path_checksum: the work vectors are filled with a function of the global cell index, the scalars are set by hand and ONE
@@ -649,6 +679,33 @@ int cup3d_debug_ctl_step(int step, double *io, const double *totals) {
   if (step == 1) ctl_step1(c, totals); else ctl_step2(c, totals);
   io[0] = c.alpha; io[1] = c.beta; io[2] = c.omega; io[3] = c.r0r_prev; io[4] = c.norm; io[5] = c.init_norm; io[6] = c.min_norm;
   io[9] = c.state; io[10] = c.restarts; io[12] = c.xcur; io[13] = c.xopt; io[14] = c.iter;
+  return CUP3D_OK;
+}
+
+// TEST SUPPORT: what the last cup3d_poisson_solve on this sim left behind (include/cup3d_hip_testing.h says which entries are live)
+int cup3d_debug_solver_state(cup3d_sim_t *h, double *io, double *totals) {
+  if (!h || !io || !totals) return CUP3D_EINVAL;
+  const Sim *s = reinterpret_cast<const Sim *>(h);
+  if (!s->dbg_solver.valid) { set_error("cup3d_debug_solver_state: no cup3d_poisson_solve has completed on this sim"); return CUP3D_ESTATE; }
+  memcpy(io, s->dbg_solver.io, sizeof s->dbg_solver.io);
+  memcpy(totals, s->dbg_solver.totals, sizeof s->dbg_solver.totals);
+  return CUP3D_OK;
+}
+int cup3d_debug_solver_vector(cup3d_sim_t *h, int which, double *host_out) {
+  if (!h || !host_out || which < 0 || which >= NVEC) return CUP3D_EINVAL;
+  Sim *s = reinterpret_cast<Sim *>(h);
+  if (!s->dbg_solver.valid) { set_error("cup3d_debug_solver_vector: no cup3d_poisson_solve has completed on this sim"); return CUP3D_ESTATE; }
+  // the two x buffers are sv[X_] and sv[XOPT]; SolverCtl::xcur / xopt (io[12], io[13]) say which holds x and which the snapshot
+  const int xcur = (int)s->dbg_solver.io[12], xopt = (int)s->dbg_solver.io[13];
+  int buf = which;
+  if (which == X_) buf = xcur ? XOPT : X_;
+  if (which == XOPT) {
+    if (xopt < 0) { set_error("cup3d_debug_solver_vector: the solve recorded no x_opt"); return CUP3D_ESTATE; }
+    buf = xopt ? XOPT : X_;
+  }
+  if (s->nb == 0) return CUP3D_OK;
+  CUP3D_HIP(hipStreamSynchronize(stream()));
+  CUP3D_HIP(hipMemcpy(host_out, s->sv[buf], (size_t)s->nb * 512 * sizeof(double), hipMemcpyDeviceToHost));
   return CUP3D_OK;
 }
 #endif

@@ -158,6 +158,11 @@ struct Sim {
   Pinned<void> h_ctl;
   void *h_ctl_dev = nullptr;
   unsigned ctl_seq = 0;
+#ifdef CUP3D_TESTING
+  // cup3d_debug_solver_state / cup3d_debug_solver_vector: the scalars (layout of cup3d_debug_ctl_step) and the totals the last
+  // cup3d_poisson_solve on this sim ended with (Solver::finish, poisson.hip); test builds only
+  struct { bool valid = false; double io[16]; double totals[9]; } dbg_solver;
+#endif
   unsigned n_restrict = 0, n_prolong = 0;
   Dev<int32_t> d_fix_blocks;  // [n_fix_blocks][6]: per block with a corrected (coarse-side) face, the interface face behind each of its six faces or -1
   unsigned n_fix_blocks = 0;

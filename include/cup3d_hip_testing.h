@@ -29,6 +29,30 @@ CUP3D_API int cup3d_debug_block_cg_iterations(cup3d_sim_t *, int32_t *per_block)
  * io[16] = alpha, beta, omega, r0r_prev, norm, init_norm, min_norm, tol, tol_rel, state (0 run, 1 done, 2 restart), restarts,
  * max_restarts, xcur, xopt, iter; step 1 takes totals[2] (main.cpp:14493), step 2 totals[7] (14558-14601) */
 CUP3D_API int cup3d_debug_ctl_step(int step, double *io, const double *totals);
+/* What the last cup3d_poisson_solve on this sim left behind -- with max_iter = m and tol = tol_rel = 0 that is the solver's state after
+ * exactly m iterations (tests/test_gpu_bicgstab_iteration.py).  Saved by the testing build when a solve returns; CUP3D_ESTATE before one has.
+ *
+ * cup3d_debug_solver_vector: one work vector, slot order, nblocks*512 doubles (host memory).  `which` counts the logical vectors in
+ * the order of poisson_vector.hpp: 0 phat, 1 rhat, 2 shat, 3 what, 4 zhat, 5 qhat, 6 s, 7 w, 8 z, 9 t, 10 v, 11 q, 12 r, 13 y, 14 x, 15 r0,
+ * 16 b, 17 x_opt.  The two x buffers swap roles during a solve (SolverCtl::xcur / xopt, ctl_xwrite); 14 and 17 are resolved to the
+ * buffer that holds the iterate / the snapshot (17: CUP3D_ESTATE when the solve recorded none).
+ *   LIVE when a solve returns: every vector but t, with the values of main.cpp:14404-14616 after that iteration.  t = A what (14549)
+ *   is live only where the LHS is a launch of its own (multi-level meshes, block solvers without a fused kernel, "no_fuse",
+ *   "no_fuse_lhs") or after a restart; where the loop kernels form the LHS themselves (uniform grids) the first loop of the NEXT
+ *   iteration forms it, so t is then the t of the iteration before (A what_{m-1}), and after an every-50th iteration in its
+ *   k_refresh form it is older still.  v is A zhat of the last iteration everywhere.
+ *
+ * cup3d_debug_solver_state: io[16] in the layout of cup3d_debug_ctl_step, as Solver::finish holds it; io[15] = 1 when the last
+ * iteration ended in the restart of 14567-14593.  totals[9] = the first seven doubles of the reduction buffer when the solve
+ * returned, then q.y, y.y:
+ *   [0..6]  r0.r, r0.w, r0.s, r0.z, |r|^2, |r0|^2, |r|^2 the scalars were last stepped from (14546; all-reduced over ranks).  The first
+ *           loop's totals share [0], [1] and are gone by then.  After a restart [0], [1] hold r0.r0 and r0.w of 14578-14581 instead
+ *           ([2..6] stay); after max_iter = 0 they hold r0.r0, r0.w of 14436-14440 and the rest is not meaningful.
+ *   [7], [8] q.y, y.y (14486) where the host stepped omega from them: host-driven iterations (every 50th, block solvers without a
+ *           fused kernel, "no_fuse").  NaN after a fused iteration: there the kernel that totals them steps omega on the device and
+ *           the second loop's totals overwrite them. */
+CUP3D_API int cup3d_debug_solver_vector(cup3d_sim_t *, int which, double *host_out);
+CUP3D_API int cup3d_debug_solver_state(cup3d_sim_t *, double *io, double *totals);
 /* the multigrid option's level hierarchies of all `nranks` ranks for the leaf ownership `owner[nblocks]` of a global multi-level mesh,
  * checked against each other (tables in range, exchange plans symmetric node for node, every ancestor's octants complete); no GPU */
 CUP3D_API int cup3d_debug_mg_plan_check(const cup3d_grid_t *mesh, const int32_t *owner, int nranks);

@@ -77,6 +77,12 @@ class ObstacleSurface(C.Structure):
                 ("cm", C.c_double * 3), ("vel", C.c_double * 3), ("omega", C.c_double * 3), ("points", C.c_void_p), ("qoi", C.c_void_p)]
 
 
+class ObstacleForces(C.Structure):
+    """cup3d_obstacle_forces"""
+    _fields_ = [("cm", C.c_double * 3), ("vel", C.c_double * 3), ("omega", C.c_double * 3), ("points", C.c_void_p), ("qoi", C.c_void_p),
+                ("totals", C.c_double * 19), ("Pthrust", C.c_double), ("Pdrag", C.c_double), ("EffPDef", C.c_double), ("EffPDefBnd", C.c_double)]
+
+
 class ObstacleShape(C.Structure):
     """cup3d_obstacle_shape"""
     _fields_ = [("nblocks", C.c_long), ("slots", C.c_void_p), ("sdf", C.c_void_p), ("udef", C.c_void_p), ("chi", C.c_void_p),
@@ -186,6 +192,8 @@ SIGNATURES = {
     "cup3d_update_tmpv_resident": (C.c_int, [_vp, C.c_int]),
     "cup3d_compute_forces": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
     "cup3d_compute_forces_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, C.POINTER(ObstacleSurface)]),
+    "cup3d_compute_forces_resident": (C.c_int, [_vp, C.c_double, C.c_int, C.POINTER(ObstacleForces)]),
+    "cup3d_compute_forces_resident_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, C.POINTER(ObstacleForces)]),
     "cup3d_profile_enable": (C.c_int, [C.c_int]),
     "cup3d_profile_reset": (C.c_int, []),
     "cup3d_profile_read": (C.c_int, [C.POINTER(ProfileEntry), C.c_int, C.POINTER(C.c_int)]),

@@ -5,7 +5,8 @@
 // cup3d_create_obstacles turns the signed distance into chi, surface points and momentum-free udef, and the other kernels take the
 // ObstacleBlocks of one obstacle at a time -- chi[8][8][8] and udef[8][8][8][3] in the reference's own (AoS) layout -- so the
 // velocity does not have to leave HBM between AdvectionDiffusion and PressureProjection when obstacles are present.  The *_resident
-// entry points run UpdateObstacles, Penalization and kernelUpdateTmpV on the blocks cup3d_create_obstacles keeps, all obstacles at once.
+// entry points run UpdateObstacles, Penalization, kernelUpdateTmpV and ComputeForces (with Obstacle::computeForces, 13079-13115) on the
+// blocks cup3d_create_obstacles keeps, all obstacles at once.
 // Velocities and tmpV are bit-exact with the reference; the penalisation force / torque sums are reductions (block totals summed in block
 // order on the host, cells within a block in tree order on the device); the momenta of UpdateObstacles and the surface sums of
 // ComputeForces are added in the reference's own order and are bit-exact per block.
@@ -13,7 +14,7 @@
 // One translation unit per operator, each with its kernels, host half and entry points:
 //   obstacles_penalization.hip  cup3d_penalization, cup3d_update_tmpv and their *_resident forms; the shared host helpers below
 //   obstacles_update.hip        cup3d_update_obstacles, cup3d_update_obstacles_resident
-//   obstacles_forces.hip        cup3d_compute_forces, cup3d_compute_forces_over_ranks
+//   obstacles_forces.hip        cup3d_compute_forces, cup3d_compute_forces_over_ranks and their *_resident forms
 //   obstacles_create.hip        cup3d_create_obstacles; the retained set and its plan
 //   obstacles_collisions.hip    cup3d_prevent_colliding_obstacles
 // This header is theirs alone: what more than one of them uses.
@@ -86,18 +87,43 @@ struct ResidentPlan {
   size_t bytes = 0;
 };
 
+// How cup3d_compute_forces_resident walks the surface of the retained set; built by its first call after a cup3d_create_obstacles, kept
+// with the set like the ResidentPlan (which it needs: the obstacles' array pointers and rigid state are that plan's tables).
+// A surface row stands for a listed block with surface points, first_h[i + 1] > first_h[i], in obstacle order and then listed order;
+// its points are [row_first[r], row_first[r + 1]) of ijk / dchi, which k_retained_surface rebuilds from the retained sdfLab and chi.
+// The distinct slots of the surface rows, ascending, are the tiles of a call: row_tile[r] is the place of row r's slot among them, and
+// the slot-major schedule lists the rows of tile j, in ascending obstacle order, at sched_rows[sched_first[j] .. sched_first[j + 1]).
+// With N obstacles, Rs surface rows and P points the device holds N * 8 + Rs * (5 * 4 + 19 * 8) + 4 + P * (3 * 4 + 3 * 8) bytes; the
+// S distinct slots and where their rows begin stay on the host, which cuts the chunks.  Rs = 0: nothing, and nothing is launched.
+struct SurfacePlan {
+  long rows = 0, ntiles = 0, npoints = 0;  // Rs, S, P
+  std::vector<long> row_base;              // [N + 1] first surface row of every obstacle
+  std::vector<int32_t> row_slot;           // [Rs] the slot of a row, for the sums in slot order
+  std::vector<int32_t> first_h;            // [Rs + 1] = row_first
+  std::vector<int32_t> tile_slots;         // [S] ascending
+  std::vector<int32_t> sched_first;        // [S + 1]
+  Dev<void> sdf;                           // const double *[N]: the retained sdfLab of every obstacle
+  Dev<void> row_obst, row_block, row_tile, sched_rows;  // int32 [Rs]
+  Dev<void> row_first;                     // int32 [Rs + 1]
+  Dev<void> ijk, dchi;                     // int32 [P][3], double [P][3]
+  Dev<void> qoi;                           // double [Rs][19]: the blocks' nineteen sums, zero when the plan is built, kept between calls
+  size_t bytes = 0;
+};
+
 // The ShapeWork buffers of the last successful cup3d_create_obstacles that the collision model and the resident operators read, moved
 // here instead of freed.
 struct RetainedObstacles {
   struct One {
     long nblocks = 0;
     std::vector<int32_t> slots_h;       // the caller's slot list, for the intersections and the plan
+    std::vector<int32_t> first_h;       // [n + 1] the CSR of the obstacle's surface points over its listed blocks, for the surface plan
     Dev<void> slots, geom, sdf, chi, udef;  // [n], [n][4], [n][10][10][10], [n][8][8][8], [n][8][8][8][3] (corrected)
   };
   std::vector<One> obst;
   ResidentPlan *plan = nullptr;  // nullptr until a resident operator asks for it
-  size_t bytes = 0;  // counted in Sim::bytes, the plan's included once it exists
-  ~RetainedObstacles() { delete plan; }
+  SurfacePlan *surface = nullptr;  // nullptr until cup3d_compute_forces_resident asks for it
+  size_t bytes = 0;  // counted in Sim::bytes, the plans' included once they exist
+  ~RetainedObstacles() { delete plan; delete surface; }
 };
 
 struct PlanItems {
@@ -112,6 +138,17 @@ int retained_for(Sim *s, const char *who, int nobst, RetainedObstacles **out);
 // the plan of the retained set, built on first use
 int resident_plan(Sim *s, RetainedObstacles *R, ResidentPlan **out);
 PlanItems plan_items(const ResidentPlan *P);
+
+struct SurfacePlanItems {
+  const int32_t *row_obst, *row_block, *row_tile, *row_first, *sched_rows;  // [Rs], [Rs], [Rs], [Rs + 1], [Rs]
+  const int32_t *ijk;   // [P][3]
+  const double *dchi;   // [P][3]
+  double *qoi;          // [Rs][19]
+  long npoints;         // P
+};
+// the surface plan of the retained set, built on first use: the tables, then ijk and dchi by k_retained_surface
+int surface_plan(Sim *s, RetainedObstacles *R, SurfacePlan **out);
+SurfacePlanItems surface_plan_items(const SurfacePlan *P);
 
 // The plan's tables are written before the launch and only read by the kernels.  Read through the constant address space, a load at a
 // wave-uniform index is a scalar load whatever the kernel stores in between, and what it returns -- the row, its obstacle, the obstacle's

@@ -1,4 +1,4 @@
-// cup3d_create_obstacles.  The grid half of CreateObstacles::operator() (main.cpp:13596-13619): the chi field cleared,
+// cup3d_create_obstacles; the retained set, its plan and its surface plan.  The grid half of CreateObstacles::operator() (main.cpp:13596-13619): the chi field cleared,
 // KernelCharacteristicFunction::operate (13298-13403), kernelComputeGridCoM (13406-13425), _kernelIntegrateUdefMomenta (13426-13488),
 // kernelAccumulateUdefMomenta (13495-13550) and kernelRemoveUdefMomenta (13551-13588) from the signed distance the obstacle's geometry
 // left in ObstacleBlock::sdfLab.  The staging is per call, as in cup3d_penalization.
@@ -30,6 +30,37 @@ struct ShapeItems {
   double *delta;         // [n][512]
 };
 
+// One cell of the surface loop of KernelCharacteristicFunction::operate (13355-13400) from sdfLab [10][10][10] and the block's chi
+// [8][8][8], both in LDS: whether (x, y, z) is a surface point, and its Delta and grad U.  The body of both k_characteristic and
+// k_retained_surface.
+__device__ __forceinline__ bool surface_cell(const double *sdf, const double *chi, int x, int y, int z, double inv2h, double fac1, double *Delta,
+                                             double *gUX, double *gUY, double *gUZ) {
+  const double EPS = DBL_EPSILON;
+  auto S = [&](int k, int j, int i) { return sdf[((k + 1) * 10 + (j + 1)) * 10 + (i + 1)]; };
+  auto X = [&](int k, int j, int i) { return chi[(k * 8 + j) * 8 + i]; };
+  const double gradUX = inv2h * (S(z, y, x + 1) - S(z, y, x - 1));
+  const double gradUY = inv2h * (S(z, y + 1, x) - S(z, y - 1, x));
+  const double gradUZ = inv2h * (S(z + 1, y, x) - S(z - 1, y, x));
+  const double gradUSq = gradUX * gradUX + gradUY * gradUY + gradUZ * gradUZ + EPS;
+  const double gradHX = (x == 0) ? 2.0 * (-0.5 * X(z, y, x + 2) + 2.0 * X(z, y, x + 1) - 1.5 * X(z, y, x))
+                                 : ((x == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z, y, x - 1) + 0.5 * X(z, y, x - 2)) : (X(z, y, x + 1) - X(z, y, x - 1)));
+  const double gradHY = (y == 0) ? 2.0 * (-0.5 * X(z, y + 2, x) + 2.0 * X(z, y + 1, x) - 1.5 * X(z, y, x))
+                                 : ((y == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z, y - 1, x) + 0.5 * X(z, y - 2, x)) : (X(z, y + 1, x) - X(z, y - 1, x)));
+  const double gradHZ = (z == 0) ? 2.0 * (-0.5 * X(z + 2, y, x) + 2.0 * X(z + 1, y, x) - 1.5 * X(z, y, x))
+                                 : ((z == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z - 1, y, x) + 0.5 * X(z - 2, y, x)) : (X(z + 1, y, x) - X(z - 1, y, x)));
+  bool accepted = false;
+  *Delta = 0.0;
+  if (!(gradHX * gradHX + gradHY * gradHY + gradHZ * gradHZ < 1e-12)) {
+    const double numD = gradHX * gradUX + gradHY * gradUY + gradHZ * gradUZ;
+    *Delta = fac1 * numD / gradUSq;
+    accepted = *Delta > EPS;
+  }
+  *gUX = gradUX;
+  *gUY = gradUY;
+  *gUZ = gradUZ;
+  return accepted;
+}
+
 __global__ void __launch_bounds__(64) k_characteristic(ShapeItems it, double *__restrict__ chi_field) {
   __shared__ double sdf[1000];
   __shared__ double chi[512];
@@ -43,7 +74,6 @@ __global__ void __launch_bounds__(64) k_characteristic(ShapeItems it, double *__
   const int gp = 1;
   const int x = lane & 7, y = lane >> 3;
   auto S = [&](int k, int j, int i) { return sdf[((k + 1) * 10 + (j + 1)) * 10 + (i + 1)]; };
-  auto X = [&](int k, int j, int i) { return chi[(k * 8 + j) * 8 + i]; };
   double total = 0.0;  // lanes 0..3: mass, CoM_x, CoM_y, CoM_z
   for (int z = 0; z < 8; ++z) {
     const double d = S(z, y, x);
@@ -86,23 +116,8 @@ __global__ void __launch_bounds__(64) k_characteristic(ShapeItems it, double *__
   if (lane < 4) it.com[(size_t)b * 4 + lane] = total;
   int npoints = 0;  // the same in every lane
   for (int z = 0; z < 8; ++z) {  // 13355-13400
-    const double gradUX = inv2h * (S(z, y, x + 1) - S(z, y, x - 1));
-    const double gradUY = inv2h * (S(z, y + 1, x) - S(z, y - 1, x));
-    const double gradUZ = inv2h * (S(z + 1, y, x) - S(z - 1, y, x));
-    const double gradUSq = gradUX * gradUX + gradUY * gradUY + gradUZ * gradUZ + EPS;
-    const double gradHX = (x == 0) ? 2.0 * (-0.5 * X(z, y, x + 2) + 2.0 * X(z, y, x + 1) - 1.5 * X(z, y, x))
-                                   : ((x == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z, y, x - 1) + 0.5 * X(z, y, x - 2)) : (X(z, y, x + 1) - X(z, y, x - 1)));
-    const double gradHY = (y == 0) ? 2.0 * (-0.5 * X(z, y + 2, x) + 2.0 * X(z, y + 1, x) - 1.5 * X(z, y, x))
-                                   : ((y == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z, y - 1, x) + 0.5 * X(z, y - 2, x)) : (X(z, y + 1, x) - X(z, y - 1, x)));
-    const double gradHZ = (z == 0) ? 2.0 * (-0.5 * X(z + 2, y, x) + 2.0 * X(z + 1, y, x) - 1.5 * X(z, y, x))
-                                   : ((z == 7) ? 2.0 * (1.5 * X(z, y, x) - 2.0 * X(z - 1, y, x) + 0.5 * X(z - 2, y, x)) : (X(z + 1, y, x) - X(z - 1, y, x)));
-    bool accepted = false;
-    double Delta = 0.0;
-    if (!(gradHX * gradHX + gradHY * gradHY + gradHZ * gradHZ < 1e-12)) {
-      const double numD = gradHX * gradUX + gradHY * gradUY + gradHZ * gradUZ;
-      Delta = fac1 * numD / gradUSq;
-      accepted = Delta > EPS;
-    }
+    double Delta, gradUX, gradUY, gradUZ;
+    const bool accepted = surface_cell(sdf, chi, x, y, z, inv2h, fac1, &Delta, &gradUX, &gradUY, &gradUZ);
     const unsigned long long mask = __ballot(accepted);
     if (accepted) {  // ObstacleBlock::write (7422-7431)
       const size_t at = (size_t)b * 512 + npoints + __popcll(mask & ((1ull << lane) - 1ull));  // < 512: one place per cell at most
@@ -131,6 +146,42 @@ __global__ void __launch_bounds__(64) k_pack_surface(ShapeItems it, const int32_
       dchi[3 * to + d] = it.dchi[3 * from + d];
     }
     delta[to] = it.delta[from];
+  }
+}
+
+// The surface loop again, for one surface row of the retained set by one wavefront (SurfacePlan, obstacles.hpp): sdfLab and chi are read
+// where cup3d_create_obstacles left them, and every point goes straight to its CSR place, which the host knows from the counts that
+// call brought down.  The same statements, ballot and running count as in k_characteristic, so the same points in the same order.
+__global__ void __launch_bounds__(64) k_retained_surface(PlanItems pl, const double *const *__restrict__ sdf_of, const int32_t *__restrict__ row_obst,
+                                                          const int32_t *__restrict__ row_block, const int32_t *__restrict__ row_first,
+                                                          int32_t *__restrict__ ijk, double *__restrict__ dchi) {
+  __shared__ double sdf[1000];
+  __shared__ double chi[512];
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int k = constant(row_obst)[r], b = constant(row_block)[r];
+  const int p0 = constant(row_first)[r], p1 = constant(row_first)[r + 1];
+  const ObstItems it = plan_obstacle(pl, k);
+  const double *__restrict__ from = constant(sdf_of)[k] + (size_t)b * 1000;
+  for (int i = lane; i < 1000; i += 64) sdf[i] = from[i];
+  for (int i = lane; i < 512; i += 64) chi[i] = it.chi[(size_t)b * 512 + i];
+  __syncthreads();
+  const double h = it.geom[4 * b], inv2h = .5 / h, fac1 = .5 * h * h;  // 13299
+  const int x = lane & 7, y = lane >> 3;
+  int npoints = 0;  // the same in every lane
+  for (int z = 0; z < 8; ++z) {
+    double Delta, gradUX, gradUY, gradUZ;
+    const bool accepted = surface_cell(sdf, chi, x, y, z, inv2h, fac1, &Delta, &gradUX, &gradUY, &gradUZ);
+    const unsigned long long mask = __ballot(accepted);
+    const int at = p0 + npoints + __popcll(mask & ((1ull << lane) - 1ull));
+    if (accepted && at < p1) {  // at < p1 whenever the count is the one the host was given: the row's stretch bounds the writes regardless
+      ijk[3 * (size_t)at] = x;
+      ijk[3 * (size_t)at + 1] = y;
+      ijk[3 * (size_t)at + 2] = z;
+      dchi[3 * (size_t)at] = -Delta * gradUX;
+      dchi[3 * (size_t)at + 1] = -Delta * gradUY;
+      dchi[3 * (size_t)at + 2] = -Delta * gradUZ;
+    }
+    npoints += __popcll(mask);
   }
 }
 
@@ -461,6 +512,92 @@ PlanItems plan_items(const ResidentPlan *P) {
                    P->sched_rows.as<const int32_t>(), P->body.as<const double>()};
 }
 
+int surface_plan(Sim *s, RetainedObstacles *R, SurfacePlan **out) {
+  if (R->surface) { *out = R->surface; return CUP3D_OK; }
+  int rc;
+  ResidentPlan *P;
+  if ((rc = resident_plan(s, R, &P))) return rc;  // the obstacles' array pointers and rigid state are its tables
+  const size_t N = R->obst.size();
+  SurfacePlan *Q = new SurfacePlan;
+  struct Drop { SurfacePlan *p; ~Drop() { delete p; } } drop{Q};  // until it is handed over
+  std::vector<int32_t> row_obst, row_block;
+  Q->row_base.assign(N + 1, 0);
+  Q->first_h.assign(1, 0);
+  long npoints = 0;
+  for (size_t k = 0; k < N; ++k) {
+    const RetainedObstacles::One &o = R->obst[k];
+    if ((long)o.first_h.size() != o.nblocks + 1) { set_error("the retained obstacle %d has no surface list", (int)k); return CUP3D_ESTATE; }
+    for (long i = 0; i < o.nblocks; ++i) {
+      const long n = (long)o.first_h[i + 1] - o.first_h[i];
+      if (n <= 0) continue;
+      npoints += n;
+      if (n > 512 || npoints > INT32_MAX) { set_error("the retained obstacle %d: block %ld lists %ld surface points, %ld so far", (int)k, i, n, npoints); return CUP3D_ESTATE; }
+      row_obst.push_back((int32_t)k);
+      row_block.push_back((int32_t)i);
+      Q->row_slot.push_back(o.slots_h[i]);
+      Q->first_h.push_back((int32_t)npoints);
+    }
+    Q->row_base[k + 1] = (long)row_obst.size();
+  }
+  Q->rows = (long)row_obst.size();
+  Q->npoints = npoints;
+  if (Q->rows > 0) {
+    const size_t nr = (size_t)Q->rows, np = (size_t)npoints;
+    std::vector<int32_t> sched_rows(nr), row_tile(nr);
+    std::vector<const double *> sdf(N);
+    for (size_t k = 0; k < N; ++k) sdf[k] = R->obst[k].sdf.as<const double>();
+    for (size_t r = 0; r < nr; ++r) sched_rows[r] = (int32_t)r;
+    // rows ascend with k, so a stable sort by slot leaves every slot's rows in ascending obstacle order
+    std::stable_sort(sched_rows.begin(), sched_rows.end(), [&](int32_t a, int32_t b) { return Q->row_slot[a] < Q->row_slot[b]; });
+    for (size_t e = 0; e < nr; ++e) {
+      const int32_t slot = Q->row_slot[sched_rows[e]];
+      if (e == 0 || slot != Q->tile_slots.back()) {
+        Q->tile_slots.push_back(slot);
+        Q->sched_first.push_back((int32_t)e);
+      }
+      row_tile[sched_rows[e]] = (int32_t)Q->tile_slots.size() - 1;
+    }
+    Q->ntiles = (long)Q->tile_slots.size();
+    Q->sched_first.push_back((int32_t)nr);
+    // what the kernels index with, against its bound, before any of it is on the device
+    for (size_t r = 0; r < nr; ++r) {
+      const bool ok = row_obst[r] >= 0 && (size_t)row_obst[r] < N && row_block[r] >= 0 && row_block[r] < R->obst[row_obst[r]].nblocks && row_tile[r] >= 0 &&
+                      row_tile[r] < Q->ntiles && Q->first_h[r] >= 0 && Q->first_h[r] < Q->first_h[r + 1] && Q->first_h[r + 1] <= npoints && Q->row_slot[r] >= 0 &&
+                      Q->row_slot[r] < s->nb && sched_rows[r] >= 0 && (size_t)sched_rows[r] < nr;
+      if (!ok) { set_error("the surface plan's row %ld is out of bounds", (long)r); return CUP3D_ESTATE; }
+    }
+    if ((rc = Q->sdf.upload(sdf.data(), N * sizeof(const double *), stream(), IfEmpty::eight_bytes)) ||
+        (rc = Q->row_obst.upload(row_obst.data(), nr * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+        (rc = Q->row_block.upload(row_block.data(), nr * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+        (rc = Q->row_tile.upload(row_tile.data(), nr * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+        (rc = Q->sched_rows.upload(sched_rows.data(), nr * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+        (rc = Q->row_first.upload(Q->first_h.data(), (nr + 1) * sizeof(int32_t), stream(), IfEmpty::eight_bytes)) ||
+        (rc = Q->ijk.alloc(np * 3 * sizeof(int32_t), IfEmpty::eight_bytes)) || (rc = Q->dchi.alloc(np * 3 * sizeof(double), IfEmpty::eight_bytes)) ||
+        (rc = Q->qoi.alloc_zeroed(nr * 19 * sizeof(double), stream())))
+      return rc;
+    {
+      ProfileScope ps("retained_surface");
+      hipLaunchKernelGGL(k_retained_surface, dim3((unsigned)nr), dim3(64), 0, stream(), plan_items(P), Q->sdf.as<const double *const>(), Q->row_obst.as<const int32_t>(),
+                         Q->row_block.as<const int32_t>(), Q->row_first.as<const int32_t>(), Q->ijk.as<int32_t>(), Q->dchi.as<double>());
+    }
+    CUP3D_HIP(hipGetLastError());
+    CUP3D_HIP(hipStreamSynchronize(stream()));  // the tables are locals
+    Q->bytes = Q->sdf.bytes() + Q->row_obst.bytes() + Q->row_block.bytes() + Q->row_tile.bytes() + Q->sched_rows.bytes() + Q->row_first.bytes() + Q->ijk.bytes() +
+               Q->dchi.bytes() + Q->qoi.bytes();
+  }
+  drop.p = nullptr;
+  R->surface = Q;
+  R->bytes += Q->bytes;
+  s->bytes += Q->bytes;
+  *out = Q;
+  return CUP3D_OK;
+}
+
+SurfacePlanItems surface_plan_items(const SurfacePlan *Q) {
+  return SurfacePlanItems{Q->row_obst.as<const int32_t>(), Q->row_block.as<const int32_t>(), Q->row_tile.as<const int32_t>(), Q->row_first.as<const int32_t>(),
+                          Q->sched_rows.as<const int32_t>(), Q->ijk.as<const int32_t>(), Q->dchi.as<const double>(), Q->qoi.as<double>(), Q->npoints};
+}
+
 }  // namespace cup3d
 
 using namespace cup3d;
@@ -484,6 +621,7 @@ extern "C" int cup3d_create_obstacles(cup3d_sim_t *h, int nobst, cup3d_obstacle_
     RetainedObstacles::One &o = R->obst[k];
     o.nblocks = shapes[k].nblocks;
     o.slots_h.assign(shapes[k].slots, shapes[k].slots + o.nblocks);
+    o.first_h = std::move(W.first_h);  // the points per block, for the surface plan of cup3d_compute_forces_resident: no device byte
     o.slots = std::move(W.slots);
     o.geom = std::move(W.geom);
     o.sdf = std::move(W.sdf);

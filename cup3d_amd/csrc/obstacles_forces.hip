@@ -7,6 +7,9 @@
 // order onto a running total they keep in a register.  No tree, no atomic: the sums are the reference's bit for bit.
 // Of the nineteen sums the functor zeroes eleven at entry (12283-12293); forcey, forcez, forcey_P, forcez_P, forcey_V, forcez_V, PoutBnd
 // and defPowerBnd go on from what the block held, so qoi is in/out.
+// cup3d_compute_forces_resident / cup3d_compute_forces_resident_over_ranks: the same on the blocks cup3d_create_obstacles retained
+// (k_surface_forces_set: one wavefront per surface row of the SurfacePlan, all obstacles of a chunk of tiles in one launch; the tiles are
+// built once per distinct slot), followed by Obstacle::computeForces (13079-13115): rows in blockID order, the ranks, 13108-13114.
 // Kept as written: the `sx` in the 2-point branch of dveldy (12364) and the precedence of the mixed derivatives' fallback,
 // sx*sy*(a - b) - (c - d) (12394-12395, 12406-12407, 12418-12419).
 #include "obstacles.hpp"
@@ -87,16 +90,33 @@ __device__ __forceinline__ void surface_gradient_row(const double *__restrict__ 
   *ddz = dz1 + dz2 * ez + dxz * ex + dyz * ey;
 }
 
-__global__ void __launch_bounds__(64) k_surface_forces(SurfItems it, const double *__restrict__ pres, double nu, double cm0, double cm1, double cm2, double u0,
-                                                        double u1, double u2, double o0, double o1, double o2) {
-  __shared__ double sm[kQoI][64];
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const double h = it.geom[4 * b];
-  const double *__restrict__ VT = it.vel + (size_t)b * 12288;
-  const double *__restrict__ XT = it.chi + (size_t)b * 4096;
-  const int p0 = it.first[b], p1 = it.first[b + 1];
+// What one wavefront reads and writes of the ObstacleBlock it evaluates
+struct SurfBlock {
+  const double *geom;    // [4] of the block: h, origin[3]
+  const int32_t *ijk;    // [..][3] the list that holds the block's points [p0, p1)
+  const double *dchi;    // [..][3]
+  int p0, p1;
+  const double *udef;    // [8][8][8][3] of the block
+  const double *pres;    // [8][8][8] of the block's slot in the resident field
+  const double *vel;     // [16][16][16][3] tile
+  const double *chi;     // [16][16][16] tile
+  double *points;        // [19][np]; may be null where kPointsOptional
+  size_t np;
+  double *qoi;           // [19] of the block, in/out
+};
+
+// KernelComputeForces::visit on one ObstacleBlock by one wavefront.  The body of both k_surface_forces and k_surface_forces_set;
+// kPointsOptional: the per-point arrays are stored only if B.points is not null (the same in every lane).
+template <bool kPointsOptional>
+__device__ __forceinline__ void surface_forces_block(const SurfBlock &B, double nu, double cm0, double cm1, double cm2, double u0, double u1, double u2, double o0,
+                                                     double o1, double o2, double (*sm)[64] /* LDS [19][64] */) {
+  const int lane = threadIdx.x;
+  const double h = B.geom[0];
+  const double *__restrict__ VT = B.vel;
+  const double *__restrict__ XT = B.chi;
+  const int p0 = B.p0, p1 = B.p1;
   double total = 0.0;  // lanes 0..18: the running sum of quantity `lane`
-  if (lane < kQoI && ((kQoICarried >> lane) & 1u)) total = it.qoi[(size_t)b * kQoI + lane];
+  if (lane < kQoI && ((kQoICarried >> lane) & 1u)) total = B.qoi[lane];
   double velUnit0 = 0., velUnit1 = 0., velUnit2 = 0.;
   const double vel_norm = sqrt(u0 * u0 + u1 * u1 + u2 * u2);
   if (vel_norm > 1e-9) {
@@ -108,9 +128,9 @@ __global__ void __launch_bounds__(64) k_surface_forces(SurfItems it, const doubl
   for (int base = p0; base < p1; base += 64) {
     const int i = base + lane;
     if (i < p1) {
-      const int ix = it.ijk[3 * (size_t)i], iy = it.ijk[3 * (size_t)i + 1], iz = it.ijk[3 * (size_t)i + 2];
-      const double px = it.geom[4 * b + 1] + h * (ix + 0.5), py = it.geom[4 * b + 2] + h * (iy + 0.5), pz = it.geom[4 * b + 3] + h * (iz + 0.5);
-      const double normX = it.dchi[3 * (size_t)i], normY = it.dchi[3 * (size_t)i + 1], normZ = it.dchi[3 * (size_t)i + 2];
+      const int ix = B.ijk[3 * (size_t)i], iy = B.ijk[3 * (size_t)i + 1], iz = B.ijk[3 * (size_t)i + 2];
+      const double px = B.geom[1] + h * (ix + 0.5), py = B.geom[2] + h * (iy + 0.5), pz = B.geom[3] + h * (iz + 0.5);
+      const double normX = B.dchi[3 * (size_t)i], normY = B.dchi[3 * (size_t)i + 1], normZ = B.dchi[3 * (size_t)i + 2];
       const double norm = 1.0 / sqrt(normX * normX + normY * normY + normZ * normZ);
       const double dx = normX * norm, dy = normY * norm, dz = normZ * norm;
       int x = ix, y = iy, z = iz;
@@ -134,37 +154,39 @@ __global__ void __launch_bounds__(64) k_surface_forces(SurfItems it, const doubl
       surface_gradient_row(VT + 1, x, y, z, sx, sy, sz, ex, ey, ez, &dvdx, &dvdy, &dvdz);
       surface_gradient_row(VT + 2, x, y, z, sx, sy, sz, ex, ey, ez, &dwdx, &dwdy, &dwdz);
       const int cell = (iz * 8 + iy) * 8 + ix;
-      const double P = pres[(size_t)it.slots[b] * 512 + cell];
+      const double P = B.pres[cell];
       const double fXV = _1oH * (dudx * normX + dudy * normY + dudz * normZ);
       const double fYV = _1oH * (dvdx * normX + dvdy * normY + dvdz * normZ);
       const double fZV = _1oH * (dwdx * normX + dwdy * normY + dwdz * normZ);
       const double fXP = -P * normX, fYP = -P * normY, fZP = -P * normZ;
       const double fXT = fXV + fXP, fYT = fYV + fYP, fZT = fZV + fZP;
-      const double *__restrict__ U = it.udef + ((size_t)b * 512 + cell) * 3;
+      const double *__restrict__ U = B.udef + (size_t)cell * 3;
       const double vxDef = U[0], vyDef = U[1], vzDef = U[2];
       const double *__restrict__ VC = VT + (((iz + 4) * 16 + (iy + 4)) * 16 + (ix + 4)) * 3;
       const double vX = VC[0], vY = VC[1], vZ = VC[2];
-      double *__restrict__ o = it.points + i;
-      const size_t np = (size_t)it.npoints;
-      o[0 * np] = px;
-      o[1 * np] = py;
-      o[2 * np] = pz;
-      o[3 * np] = P;
-      o[4 * np] = -P * dx + _1oH * (dudx * dx + dudy * dy + dudz * dz);
-      o[5 * np] = -P * dy + _1oH * (dvdx * dx + dvdy * dy + dvdz * dz);
-      o[6 * np] = -P * dz + _1oH * (dwdx * dx + dwdy * dy + dwdz * dz);
-      o[7 * np] = _1oH * (dudx * dx + dudy * dy + dudz * dz);
-      o[8 * np] = _1oH * (dvdx * dx + dvdy * dy + dvdz * dz);
-      o[9 * np] = _1oH * (dwdx * dx + dwdy * dy + dwdz * dz);
-      o[10 * np] = (dwdy - dvdz) / h;
-      o[11 * np] = (dudz - dwdx) / h;
-      o[12 * np] = (dvdx - dudy) / h;
-      o[13 * np] = vxDef;
-      o[14 * np] = vX;
-      o[15 * np] = vyDef;
-      o[16 * np] = vY;
-      o[17 * np] = vzDef;
-      o[18 * np] = vZ;
+      if (!kPointsOptional || B.points) {
+        double *__restrict__ o = B.points + i;
+        const size_t np = B.np;
+        o[0 * np] = px;
+        o[1 * np] = py;
+        o[2 * np] = pz;
+        o[3 * np] = P;
+        o[4 * np] = -P * dx + _1oH * (dudx * dx + dudy * dy + dudz * dz);
+        o[5 * np] = -P * dy + _1oH * (dvdx * dx + dvdy * dy + dvdz * dz);
+        o[6 * np] = -P * dz + _1oH * (dwdx * dx + dwdy * dy + dwdz * dz);
+        o[7 * np] = _1oH * (dudx * dx + dudy * dy + dudz * dz);
+        o[8 * np] = _1oH * (dvdx * dx + dvdy * dy + dvdz * dz);
+        o[9 * np] = _1oH * (dwdx * dx + dwdy * dy + dwdz * dz);
+        o[10 * np] = (dwdy - dvdz) / h;
+        o[11 * np] = (dudz - dwdx) / h;
+        o[12 * np] = (dvdx - dudy) / h;
+        o[13 * np] = vxDef;
+        o[14 * np] = vX;
+        o[15 * np] = vyDef;
+        o[16 * np] = vY;
+        o[17 * np] = vzDef;
+        o[18 * np] = vZ;
+      }
       // the summands of 12463-12491, in sumQoI order
       sm[0][lane] = fXT;
       sm[1][lane] = fYT;
@@ -201,7 +223,34 @@ __global__ void __launch_bounds__(64) k_surface_forces(SurfItems it, const doubl
     }
     __syncthreads();
   }
-  if (lane < kQoI) it.qoi[(size_t)b * kQoI + lane] = total;
+  if (lane < kQoI) B.qoi[lane] = total;
+}
+
+__global__ void __launch_bounds__(64) k_surface_forces(SurfItems it, const double *__restrict__ pres, double nu, double cm0, double cm1, double cm2, double u0,
+                                                        double u1, double u2, double o0, double o1, double o2) {
+  __shared__ double sm[kQoI][64];
+  const int b = blockIdx.x;
+  const SurfBlock B{it.geom + 4 * (size_t)b, it.ijk, it.dchi, it.first[b], it.first[b + 1], it.udef + (size_t)b * 1536, pres + (size_t)it.slots[b] * 512,
+                    it.vel + (size_t)b * 12288, it.chi + (size_t)b * 4096, it.points, (size_t)it.npoints, it.qoi + (size_t)b * kQoI};
+  surface_forces_block<false>(B, nu, cm0, cm1, cm2, u0, u1, u2, o0, o1, o2, sm);
+}
+
+// The same for the surface rows of the retained set (SurfacePlan, obstacles.hpp), all obstacles of a chunk of tiles in one launch:
+// workgroup j evaluates scheduled row e0 + j.  The row's obstacle, block, tile and point range come from the plan's tables, udef is read
+// where cup3d_create_obstacles left it, cm / vel / omega from the plan's body table, the tile is number row_tile - tile0 of the scratch,
+// and the nineteen sums are the plan's row, read and written in place.
+__global__ void __launch_bounds__(64) k_surface_forces_set(PlanItems pl, SurfacePlanItems sp, int e0, int tile0, const double *__restrict__ vel_tiles,
+                                                            const double *__restrict__ chi_tiles, const double *__restrict__ pres, double nu,
+                                                            double *__restrict__ points /* [19][P] or null */) {
+  __shared__ double sm[kQoI][64];
+  const int r = constant(sp.sched_rows)[e0 + blockIdx.x];
+  const int k = constant(sp.row_obst)[r], b = constant(sp.row_block)[r], t = constant(sp.row_tile)[r] - tile0;
+  const ObstItems it = plan_obstacle(pl, k);
+  Constant<double> *body = constant(pl.body) + 9 * (size_t)k;
+  const SurfBlock B{it.geom + 4 * (size_t)b, sp.ijk, sp.dchi, constant(sp.row_first)[r], constant(sp.row_first)[r + 1], it.udef + (size_t)b * 1536,
+                    pres + (size_t)it.slots[b] * 512, vel_tiles + (size_t)t * 12288, chi_tiles + (size_t)t * 4096, points, (size_t)sp.npoints,
+                    sp.qoi + (size_t)r * kQoI};
+  surface_forces_block<true>(B, nu, body[0], body[1], body[2], body[3], body[4], body[5], body[6], body[7], body[8], sm);
 }
 
 // device buffers of cup3d_compute_forces, kept in the sim and only ever grown: the tile scratch of one chunk of blocks and the staged
@@ -297,6 +346,132 @@ int scratch_for(Sim *s, long m) {
   if ((rc = s->forces->vel.need((size_t)m * 12288 * sizeof(double), s)) || (rc = s->forces->chi.need((size_t)m * 4096 * sizeof(double), s))) return rc;
   return CUP3D_OK;
 }
+
+// the largest block count of a rank, read off `owner`, in chunks: the rounds of collective tile calls every rank makes
+long rounds_over_ranks(const Sim *s, const Grid *gm, const int32_t *owner, long chunk) {
+  long most = 0;
+  std::vector<long> count(std::max(s->grid->nranks, 1), 0);
+  for (int64_t b = 0; b < gm->nblocks(); ++b)
+    if (owner[b] >= 0 && owner[b] < (int32_t)count.size()) most = std::max(most, ++count[owner[b]]);
+  return (most + chunk - 1) / chunk;
+}
+
+// Obstacle::computeForces from 13108 on, with the EPS in scope there (12811)
+void derived_powers(cup3d_obstacle_forces &o) {
+  const double EPS = DBL_EPSILON;
+  const double thrust = o.totals[13], drag = o.totals[12], defPower = o.totals[16], defPowerBnd = o.totals[17];
+  const double vel_norm = std::sqrt(o.vel[0] * o.vel[0] + o.vel[1] * o.vel[1] + o.vel[2] * o.vel[2]);
+  o.Pthrust = thrust * vel_norm;
+  o.Pdrag = drag * vel_norm;
+  o.EffPDef = o.Pthrust / (o.Pthrust - std::min(defPower, (double)0) + EPS);
+  o.EffPDefBnd = o.Pthrust / (o.Pthrust - defPowerBnd + EPS);
+}
+
+// cup3d_compute_forces_resident (mesh == nullptr) and cup3d_compute_forces_resident_over_ranks
+int forces_resident(cup3d_sim_t *h, const cup3d_grid_t *mesh, const int32_t *owner, double nu, int nobst, cup3d_obstacle_forces *out) {
+  const bool over_ranks = mesh != nullptr;
+  const char *who = over_ranks ? "cup3d_compute_forces_resident_over_ranks" : "cup3d_compute_forces_resident";
+  Sim *s = reinterpret_cast<Sim *>(h);
+  const long chunk = forces_chunk(over_ranks);
+  const long rounds = over_ranks ? rounds_over_ranks(s, reinterpret_cast<const Grid *>(mesh), owner, chunk) : 0;
+  bool want_points = false;
+  for (int k = 0; k < nobst; ++k) want_points = want_points || out[k].points;
+  RetainedObstacles *R = nullptr;
+  ResidentPlan *P = nullptr;
+  SurfacePlan *Q = nullptr;
+  std::vector<double> table, rows;
+  // what this rank can get wrong: nothing of the call is launched before it has passed.  Over ranks a rank that fails here still takes
+  // part in the tile calls, asking for nothing, and in the all-reduces, where its flag ends the call on every rank.
+  auto prepare = [&]() -> int {
+    int rc;
+    if ((rc = retained_for(s, who, nobst, &R)) || (rc = surface_plan(s, R, &Q)) || (rc = resident_plan(s, R, &P))) return rc;
+    if (Q->rows == 0) return CUP3D_OK;
+    if ((rc = scratch_for(s, std::min(chunk, Q->ntiles)))) return rc;
+    if (want_points && (rc = s->forces->points.need((size_t)Q->npoints * kQoI * sizeof(double), s))) return rc;
+    table.resize(9 * (size_t)nobst);
+    for (int k = 0; k < nobst; ++k)
+      for (int d = 0; d < 3; ++d) {
+        table[9 * (size_t)k + d] = out[k].cm[d];
+        table[9 * (size_t)k + 3 + d] = out[k].vel[d];
+        table[9 * (size_t)k + 6 + d] = out[k].omega[d];
+      }
+    CUP3D_HIP(hipMemcpyAsync(P->body.get(), table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
+    return CUP3D_OK;
+  };
+  const int local = prepare();
+  if (local && !over_ranks) return local;
+  const std::string local_text = local ? cup3d_last_error() : "";
+  const long nrows = local ? 0 : Q->rows, ntiles = local ? 0 : Q->ntiles;
+  const long nchunks = over_ranks ? rounds : (ntiles + chunk - 1) / chunk;
+  int rc;
+  for (long c = 0; c < nchunks; ++c) {  // the tiles of `chunk` distinct slots at a time: each slot's tiles are built once, whoever holds it
+    const long t0 = c * chunk, m = std::max(0L, std::min(chunk, ntiles - t0));
+    const int32_t *slots = m ? Q->tile_slots.data() + t0 : nullptr;
+    void *vel = m ? s->forces->vel.get() : nullptr, *chi = m ? s->forces->chi.get() : nullptr;
+    if (over_ranks) {
+      if ((rc = cup3d_sim_labs_over_ranks_device(h, mesh, owner, CUP3D_FIELD_VEL, m, slots, 4, 1, -1, vel)) ||
+          (rc = cup3d_sim_labs_over_ranks_device(h, mesh, owner, CUP3D_FIELD_CHI, m, slots, 4, 1, -1, chi)))
+        return rc;
+    } else if ((rc = cup3d_sim_labs_device(h, CUP3D_FIELD_VEL, m, slots, 4, 1, -1, vel)) || (rc = cup3d_sim_labs_device(h, CUP3D_FIELD_CHI, m, slots, 4, 1, -1, chi))) {
+      return rc;
+    }
+    if (m == 0) continue;
+    const int e0 = Q->sched_first[t0], e1 = Q->sched_first[t0 + m];  // the slot-major schedule: a chunk of tiles is a range of scheduled rows
+    ProfileScope ps("surface_forces_set");
+    hipLaunchKernelGGL(k_surface_forces_set, dim3((unsigned)(e1 - e0)), dim3(64), 0, stream(), plan_items(P), surface_plan_items(Q), e0, (int)t0,
+                       s->forces->vel.as<const double>(), s->forces->chi.as<const double>(), (const double *)s->pres, nu,
+                       want_points ? s->forces->points.as<double>() : (double *)nullptr);
+    CUP3D_HIP(hipGetLastError());
+  }
+  if (nrows > 0) {
+    rows.resize((size_t)nrows * kQoI);
+    {
+      ProfileScope ps("surface_forces_download");
+      CUP3D_HIP(hipMemcpyAsync(rows.data(), Q->qoi.get(), rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    }
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    stats_field_download(rows.size() * sizeof(double));
+  }
+  // Obstacle::computeForces (13079-13107): the blocks' rows in blockID order, then the ranks
+  std::vector<double> totals((size_t)nobst * kQoI, 0.0);
+  Dev<void> red;  // the all-reduce operand of this call (sums_over_ranks)
+  if (scalars_cross_ranks(s) && (rc = red.alloc((kQoI + 1) * sizeof(double), IfEmpty::eight_bytes))) return rc;
+  for (int k = 0; k < nobst; ++k) {
+    double *T = &totals[(size_t)k * kQoI];
+    if (!local) {
+      const long r0 = Q->row_base[k], n = Q->row_base[k + 1] - r0;
+      // rows of blocks without points are all zero and missing here: the sum starts at +0 and never becomes -0, so that changes no bit
+      add_rows_in_slot_order(Q->row_slot.data() + r0, n, rows.data() + (size_t)r0 * kQoI, kQoI, kQoI, T);
+    }
+    if ((rc = sums_over_ranks(s, red.as<double>(), T, kQoI, false, local, who, k))) {  // MPI_Allreduce(sum, 19), 13087
+      if (local) set_error("%s", local_text.c_str());
+      return rc;
+    }
+  }
+  // every obstacle has passed: the caller's structs.  An obstacle's points are columns [p0, p0 + np) of the device's [19][P]: they come
+  // down last, straight into the arrays of the obstacles that asked, one strided copy each
+  size_t points_down = 0;
+  for (int k = 0; k < nobst; ++k) {
+    cup3d_obstacle_forces &o = out[k];
+    const long r0 = Q->row_base[k], n = Q->row_base[k + 1] - r0;
+    const size_t p0 = (size_t)Q->first_h[r0], np = (size_t)Q->first_h[r0 + n] - p0;
+    if (o.points && np) {
+      ProfileScope ps("surface_forces_download");
+      CUP3D_HIP(hipMemcpy2DAsync(o.points, np * sizeof(double), s->forces->points.as<const double>() + p0, (size_t)Q->npoints * sizeof(double), np * sizeof(double), kQoI,
+                                 hipMemcpyDeviceToHost, stream()));
+      points_down += np * kQoI * sizeof(double);
+    }
+    if (o.qoi)
+      for (size_t i = 0; i < (size_t)n * kQoI; ++i) o.qoi[i] = rows[(size_t)r0 * kQoI + i];
+    for (int q = 0; q < kQoI; ++q) o.totals[q] = totals[(size_t)k * kQoI + q];
+    derived_powers(o);
+  }
+  if (points_down) {
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    stats_field_download(points_down);
+  }
+  return CUP3D_OK;
+}
 }  // namespace
 
 }  // namespace cup3d
@@ -338,14 +513,8 @@ extern "C" int cup3d_compute_forces_over_ranks(cup3d_sim_t *h, const cup3d_grid_
   // The tile calls are collectives, so every rank has to make the same number of them per obstacle whatever its own share of the obstacle
   // is.  No rank holds more ObstacleBlocks of one obstacle than it holds blocks, and the largest block count of a rank is something every
   // rank reads off `owner`: that many blocks, chunk by chunk, is the number of rounds -- with no collective of this entry point's own.
-  long most = 0;
-  {
-    std::vector<long> count(std::max(s->grid->nranks, 1), 0);
-    for (int64_t b = 0; b < gm->nblocks(); ++b)
-      if (owner[b] >= 0 && owner[b] < (int32_t)count.size()) most = std::max(most, ++count[owner[b]]);
-  }
   const long chunk = forces_chunk(/*over_ranks=*/true);
-  const long rounds = (most + chunk - 1) / chunk;
+  const long rounds = rounds_over_ranks(s, gm, owner, chunk);
   // a rank whose own arguments are bad still takes part, asking for no tile, and reports the error afterwards: the others finish
   int bad = CUP3D_OK;
   for (int k = 0; k < nobst && !bad; ++k) {
@@ -373,4 +542,24 @@ extern "C" int cup3d_compute_forces_over_ranks(cup3d_sim_t *h, const cup3d_grid_
   }
   if (bad) { set_error("%s", bad_text.c_str()); return bad; }
   return CUP3D_OK;
+}
+
+extern "C" int cup3d_compute_forces_resident(cup3d_sim_t *h, double nu, int nobst, cup3d_obstacle_forces *obst) {
+  if (!h || nobst < 0 || (nobst > 0 && !obst)) return CUP3D_EINVAL;
+  if (nobst == 0) return CUP3D_OK;
+  Sim *s = reinterpret_cast<Sim *>(h);
+  if (s->grid->n_local >= 0 || s->grid->nranks > 1) {
+    set_error("cup3d_compute_forces_resident: this sim holds one rank's share of a grid spread over %d ranks; the tiles need cup3d_compute_forces_resident_over_ranks",
+              s->grid->nranks);
+    return CUP3D_EINVAL;
+  }
+  return forces_resident(h, nullptr, nullptr, nu, nobst, obst);
+}
+
+extern "C" int cup3d_compute_forces_resident_over_ranks(cup3d_sim_t *h, const cup3d_grid_t *mesh, const int32_t *owner, double nu, int nobst,
+                                                        cup3d_obstacle_forces *obst) {
+  if (!h || nobst < 0 || (nobst > 0 && !obst)) return CUP3D_EINVAL;
+  if (!mesh || !owner) { set_error("cup3d_compute_forces_resident_over_ranks: null mesh / owner"); return CUP3D_EINVAL; }
+  if (nobst == 0) return CUP3D_OK;
+  return forces_resident(h, mesh, owner, nu, nobst, obst);
 }

@@ -704,11 +704,18 @@ class ComputeForces(Operator):
     """ComputeForces::operator()(dt) without Obstacle::computeForces (main.cpp:12496-12503): KernelComputeForces on the device for
     sim.surfaces (ObstacleSurface list) from the resident vel, chi and pres.  Returns [(points [19][npoints], qoi [n][19])] per obstacle
     -- the 19 per-point arrays in the order pX pY pZ P fX fY fZ fxV fyV fzV omegaX omegaY omegaZ vxDef vX vyDef vY vzDef vZ and the
-    blocks' sums -- and leaves qoi in the ObstacleSurface, where the next call starts from."""
+    blocks' sums -- and leaves qoi in the ObstacleSurface, where the next call starts from.
+    With sim.resident_obstacles it is ComputeForces::operator() WITH Obstacle::computeForces (13079-13115) for sim.obstacles on the blocks
+    the last CreateObstacles left on the device (cup3d_compute_forces_resident): nothing goes up, the blocks' sums stay on the device
+    between calls, the return value has the same shape, and each ObstacleData gets surf_force, pres_force, visc_force, surf_torque, drag,
+    thrust, Pout, PoutBnd, defPower, defPowerBnd, pLocom, Pthrust, Pdrag, EffPDef, EffPDefBnd, force_totals (the nineteen sums) and the
+    returned arrays again as force_points / force_rows."""
 
     def __call__(self, dt=0, mesh=None, owner=None):
         """mesh / owner (the global mesh object and the rank of every leaf): the mesh is spread over ranks and this is a collective."""
         s = self.sim
+        if getattr(s, "resident_obstacles", False):
+            return self._resident(mesh, owner)
         surfaces = getattr(s, "surfaces", [])
         arr = (capi.ObstacleSurface * max(1, len(surfaces)))()
         out = []
@@ -727,6 +734,33 @@ class ComputeForces(Operator):
             check(lib().cup3d_compute_forces_over_ranks(s.handle, mesh.handle, ow.ctypes.data_as(C.c_void_p), float(s.nu), len(surfaces), arr))
         for o, (_, qoi) in zip(surfaces, out):
             o.qoi = qoi
+        return out
+
+    def _resident(self, mesh, owner):
+        s = self.sim
+        obstacles = s.obstacles
+        if not obstacles:
+            return []
+        arr = (capi.ObstacleForces * len(obstacles))()
+        out = []
+        for o, shape, a in zip(obstacles, s.shapes, arr):
+            per_block = np.diff(shape.first)   # the surface CreateObstacles returned: how many points and rows come back
+            points, qoi = np.zeros((19, int(per_block.sum()))), np.zeros((int((per_block > 0).sum()), 19))
+            a.points, a.qoi = points.ctypes.data, qoi.ctypes.data
+            for d in range(3):
+                a.cm[d], a.vel[d], a.omega[d] = o.cm[d], o.vel[d], o.omega[d]
+            out.append((points, qoi))
+        if mesh is None:
+            check(lib().cup3d_compute_forces_resident(s.handle, float(s.nu), len(obstacles), arr))
+        else:
+            ow = np.ascontiguousarray(owner, dtype=np.int32)
+            check(lib().cup3d_compute_forces_resident_over_ranks(s.handle, mesh.handle, ow.ctypes.data_as(C.c_void_p), float(s.nu), len(obstacles), arr))
+        for o, a, (points, qoi) in zip(obstacles, arr, out):
+            t = np.array(a.totals[:])
+            o.force_totals, o.force_points, o.force_rows = t, points, qoi   # what a pipeline, whose return values nobody sees, leaves to read
+            o.surf_force, o.pres_force, o.visc_force, o.surf_torque = t[0:3].copy(), t[3:6].copy(), t[6:9].copy(), t[9:12].copy()   # 13089-13100
+            o.drag, o.thrust, o.Pout, o.PoutBnd, o.defPower, o.defPowerBnd, o.pLocom = (float(v) for v in t[12:19])                    # 13101-13107
+            o.Pthrust, o.Pdrag, o.EffPDef, o.EffPDefBnd = float(a.Pthrust), float(a.Pdrag), float(a.EffPDef), float(a.EffPDefBnd)   # 13108-13114
         return out
 
 
@@ -844,7 +878,7 @@ class Simulation:
     """The time loop of struct Simulation restricted to the hot path (no obstacles, frozen mesh):
     calcMaxTimestep 15254-15305, advance 15306-15326, pipeline order of setupOperators 15229-15246."""
 
-    def __init__(self, sim, obstacle_operators=False, collisions=False, resident_obstacles=False):
+    def __init__(self, sim, obstacle_operators=False, collisions=False, resident_obstacles=False, forces=False):
         """obstacle_operators: with sim.obstacles, put UpdateObstacles and Penalization between the forcing and PressureProjection
         (15235-15243) -- the resident obstacle step -- and, where sim.shapes is set (ObstacleShape list), CreateObstacles in front of
         everything.  Off by default: the caller then runs Penalization itself.
@@ -852,16 +886,19 @@ class Simulation:
         CreateObstacles leaves on the device, i.e. sim.shapes.
         resident_obstacles: with obstacle_operators, UpdateObstacles, Penalization and PressureProjection's tmpV update read the blocks, chi
         and udef CreateObstacles leaves on the device instead of uploading them per obstacle (sets sim.resident_obstacles); the same
-        pipeline and the same bits.  It needs sim.shapes, so that CreateObstacles runs in front of them."""
+        pipeline and the same bits.  It needs sim.shapes, so that CreateObstacles runs in front of them.
+        forces: ComputeForces after PressureProjection, as setupOperators ends (15244), on the retained set: it needs resident_obstacles."""
+        if forces and not resident_obstacles:
+            raise ValueError("forces=True needs resident_obstacles=True: ComputeForces in the pipeline reads the blocks CreateObstacles leaves on the device")
         if resident_obstacles and not (obstacle_operators and getattr(sim, "shapes", None)):
             raise ValueError("resident_obstacles=True needs obstacle_operators=True and sim.shapes (an ObstacleShape list): the operators "
                              "read the blocks CreateObstacles leaves on the device")
-        self._bind(sim, obstacle_operators, collisions, resident_obstacles)
+        self._bind(sim, obstacle_operators, collisions, resident_obstacles, forces)
 
-    def _bind(self, sim, obstacle_operators, collisions, resident_obstacles):
+    def _bind(self, sim, obstacle_operators, collisions, resident_obstacles, forces=False):
         """the operators on `sim`: what __init__ does, and adaptMesh / adaptMeshOverRanks again on the adapted SimulationData"""
         self.sim, self.obstacle_operators, self.collisions = sim, bool(obstacle_operators), bool(collisions)
-        self.resident_obstacles = bool(resident_obstacles)
+        self.resident_obstacles, self.forces = bool(resident_obstacles), bool(forces)
         if self.resident_obstacles or hasattr(sim, "resident_obstacles"):
             sim.resident_obstacles = self.resident_obstacles
         self.pipeline = [AdvectionDiffusionImplicit(sim) if sim.implicitDiffusion else AdvectionDiffusion(sim)]  # 15231-15234
@@ -873,6 +910,8 @@ class Simulation:
         if self.obstacle_operators and (sim.obstacles or shapes):
             self.pipeline += [UpdateObstacles(sim)] + ([PreventCollidingObstacles(sim)] if self.collisions else []) + [Penalization(sim)]
         self.pipeline.append(PressureProjection(sim))
+        if self.forces:
+            self.pipeline.append(ComputeForces(sim))   # 15244
 
     def adaptMesh(self, Rtol, Ctol):
         """Simulation::adaptMesh (15179-15194) without obstacles: vorticity -> tags -> ValidStates -> Adapt.  Replaces
@@ -884,7 +923,7 @@ class Simulation:
             GradChiOnTmp(s)(0)
         st = s.grid.valid_states(MeshAdaptation(Rtol, Ctol).Tag(s, "tmpV"))
         if (st != 0).any():
-            self._bind(s.adapted(st), self.obstacle_operators, self.collisions, self.resident_obstacles)
+            self._bind(s.adapted(st), self.obstacle_operators, self.collisions, self.resident_obstacles, self.forces)
         return st
 
     def adaptMeshOverRanks(self, mesh, owner, rank, nranks, Rtol, Ctol, allgather):
@@ -906,7 +945,7 @@ class Simulation:
         if not (st != 0).any():
             return st, mesh, owner
         new, new_mesh, new_owner = s.adapted_over_ranks(mesh, owner, st, rank, nranks)
-        self._bind(new, self.obstacle_operators, self.collisions, self.resident_obstacles)
+        self._bind(new, self.obstacle_operators, self.collisions, self.resident_obstacles, self.forces)
         return st, new_mesh, new_owner
 
     def calcMaxTimestep(self):

@@ -546,6 +546,50 @@ CUP3D_API int cup3d_compute_forces(cup3d_sim_t *, double nu, int nobstacles, cup
  * part in the tile calls, asking for nothing, and then returns CUP3D_EINVAL with nothing touched; the other ranks finish. */
 CUP3D_API int cup3d_compute_forces_over_ranks(cup3d_sim_t *, const cup3d_grid_t *mesh, const int32_t *owner, double nu, int nobstacles,
                                               cup3d_obstacle_surface *obstacles);
+/* ComputeForces::operator() WITH Obstacle::computeForces (12496-12503, 13079-13115) on the RETAINED set: the last operator of the step
+ * (setupOperators, 15244).  It computes, bit for bit, what cup3d_compute_forces computes on the surface list and corrected udef that
+ * cup3d_create_obstacles returned, but nothing of that goes up: udef is read where that call left it, and the surface list is rebuilt
+ * on the device from the retained sdfLab and chi by the statements that made it (13355-13400).  Obstacle k of a call is obstacle k of
+ * the last successful cup3d_create_obstacles.
+ *   The surface plan.  The first call after a cup3d_create_obstacles builds it and keeps it with the set (counted in
+ *     cup3d_sim_device_bytes from then on, dropped with the set; it builds the plan of the resident operators above too if none of them
+ *     has run).  A surface row is a listed block with surface points, in obstacle order and then listed order.  With N obstacles, Rs
+ *     surface rows, S distinct slots among them and P points it holds N * 8 bytes (where each obstacle's sdfLab lies), Rs * (5 * 4 + 19 * 8)
+ *     + 4 bytes (obstacle, block, tile and slot-major place of a row, where each row's points begin; the blocks' nineteen sums) and
+ *     P * (3 * 4 + 3 * 8) bytes (ijk, dchi); S costs nothing on the device -- the slot list and where each slot's rows begin stay on the
+ *     host.  A rank with Rs = 0 holds an empty plan and launches nothing.
+ *   The nineteen sums of a block (7289-7307) live in the plan: zero when it is built, as ObstacleBlock's members are after create
+ *     (7311-7319, 7279-7284); each call restarts eleven and lets eight run on (12283-12293), so the second call after one
+ *     cup3d_create_obstacles returns what cup3d_compute_forces returns when handed the first call's qoi.
+ *   Tiles.  The [-4,5) tiles of vel and chi are built once per DISTINCT slot per call, 512 slots at a time (4096 over ranks), into the
+ *     scratch of cup3d_compute_forces: two tile calls and one launch per chunk, all obstacles together.
+ *   Out, per obstacle: points (may be NULL) [19][points of the obstacle on this rank] and qoi (may be NULL) [blocks with points][19], both
+ *     in the order of cup3d_compute_forces on shape.surface; totals[19] = the rows added in ascending slot order -- obstacleBlocks is
+ *     indexed by blockID, so that is the loop of 13082-13086 -- then summed over the ranks (13087); Pthrust, Pdrag, EffPDef, EffPDefBnd
+ *     as 13108-13114 write them from totals and vel.
+ *   cup3d_run_stats: field_bytes_uploaded stays 0; field_bytes_downloaded grows by Rs * 19 * 8 (one download of all rows), and by
+ *     19 * 8 bytes per point of every obstacle that passes points (one strided copy per such obstacle, straight into its array, once
+ *     every obstacle has passed).  If no obstacle passes points they are neither stored nor allocated.
+ * cup3d_compute_forces_resident_over_ranks is COLLECTIVE: every rank calls it with the same nobstacles; the tiles come from
+ * cup3d_sim_labs_over_ranks_device, in the same number of rounds on every rank PER CALL -- the largest block count of a rank, read off
+ * `owner`, in chunks of 4096 -- not per obstacle as in cup3d_compute_forces_over_ranks; then per obstacle, in obstacle order, two
+ * all-reduces (19 totals and the flag, at most 16 values each).  A rank whose own arguments fail still takes part in all of them,
+ * asking for no tile; it returns its own code, the others CUP3D_ECOMM, and every rank returns.
+ * CUP3D_EINVAL: a null handle, nobstacles < 0, a null array with nobstacles > 0, null mesh / owner, the one-rank call on a rank view or
+ * on one rank's share of a uniform grid.  CUP3D_ESTATE: no cup3d_create_obstacles has left its blocks on the device, nobstacles differs
+ * from the retained count, or a table of the plan fails its bound.  A refused call writes nothing of the caller's and launches nothing;
+ * the caller's structs are written only when every obstacle has passed.  nobstacles = 0 is a no-op. */
+typedef struct {
+  double cm[3], vel[3], omega[3];   /* in */
+  double *points;                   /* out, may be NULL: [19][points of obstacle k on this rank], order of cup3d_compute_forces */
+  double *qoi;                      /* out, may be NULL: [blocks with points][19], listed order */
+  double totals[19];                /* out: surfForce[3] presForce[3] viscForce[3] surfTorque[3] drag thrust Pout PoutBnd defPower defPowerBnd
+                                       pLocom (13089-13107) */
+  double Pthrust, Pdrag, EffPDef, EffPDefBnd;   /* out, 13108-13114 */
+} cup3d_obstacle_forces;
+CUP3D_API int cup3d_compute_forces_resident(cup3d_sim_t *, double nu, int nobstacles, cup3d_obstacle_forces *obstacles);
+CUP3D_API int cup3d_compute_forces_resident_over_ranks(cup3d_sim_t *, const cup3d_grid_t *mesh, const int32_t *owner, double nu, int nobstacles,
+                                                       cup3d_obstacle_forces *obstacles);
 /* Implicit diffusion: AdvectionDiffusionImplicit (main.cpp:7148-7157, 10030-10119), selected by -implicitDiffusion (15231-15232).
  * One call = euler(dt): KernelAdvect, the explicit-diffusion guess, KernelDiffusionRHS and one DiffusionSolver::solve per velocity
  * component.  `params`: tol / tol_rel = sim.DiffusionErrorTol / DiffusionErrorTolRel (15369-15370), max_iter; mean_constraint,

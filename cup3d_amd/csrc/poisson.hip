@@ -163,7 +163,7 @@ struct Solver {
     CUP3D_HIP(hipStreamSynchronize(stream()));
     CUP3D_HIP(hipMemcpy(D.totals, s->d_red + kRedDots, 7 * sizeof(double), hipMemcpyDeviceToHost));
     D.totals[7] = dbg_qy[0]; D.totals[8] = dbg_qy[1];
-    D.valid = !helm;
+    D.valid = true;
     return CUP3D_OK;
   }
 #else
@@ -686,7 +686,7 @@ int cup3d_debug_ctl_step(int step, double *io, const double *totals) {
 int cup3d_debug_solver_state(cup3d_sim_t *h, double *io, double *totals) {
   if (!h || !io || !totals) return CUP3D_EINVAL;
   const Sim *s = reinterpret_cast<const Sim *>(h);
-  if (!s->dbg_solver.valid) { set_error("cup3d_debug_solver_state: no cup3d_poisson_solve has completed on this sim"); return CUP3D_ESTATE; }
+  if (!s->dbg_solver.valid) { set_error("cup3d_debug_solver_state: no cup3d_poisson_solve, cup3d_diffusion_solve or cup3d_advect_diffuse_implicit has completed on this sim"); return CUP3D_ESTATE; }
   memcpy(io, s->dbg_solver.io, sizeof s->dbg_solver.io);
   memcpy(totals, s->dbg_solver.totals, sizeof s->dbg_solver.totals);
   return CUP3D_OK;
@@ -694,7 +694,7 @@ int cup3d_debug_solver_state(cup3d_sim_t *h, double *io, double *totals) {
 int cup3d_debug_solver_vector(cup3d_sim_t *h, int which, double *host_out) {
   if (!h || !host_out || which < 0 || which >= NVEC) return CUP3D_EINVAL;
   Sim *s = reinterpret_cast<Sim *>(h);
-  if (!s->dbg_solver.valid) { set_error("cup3d_debug_solver_vector: no cup3d_poisson_solve has completed on this sim"); return CUP3D_ESTATE; }
+  if (!s->dbg_solver.valid) { set_error("cup3d_debug_solver_vector: no cup3d_poisson_solve, cup3d_diffusion_solve or cup3d_advect_diffuse_implicit has completed on this sim"); return CUP3D_ESTATE; }
   // the two x buffers are sv[X_] and sv[XOPT]; SolverCtl::xcur / xopt (io[12], io[13]) say which holds x and which the snapshot
   const int xcur = (int)s->dbg_solver.io[12], xopt = (int)s->dbg_solver.io[13];
   int buf = which;

@@ -31,6 +31,10 @@ CUP3D_API int cup3d_debug_block_cg_iterations(cup3d_sim_t *, int32_t *per_block)
 CUP3D_API int cup3d_debug_ctl_step(int step, double *io, const double *totals);
 /* What the last cup3d_poisson_solve on this sim left behind -- with max_iter = m and tol = tol_rel = 0 that is the solver's state after
  * exactly m iterations (tests/test_gpu_bicgstab_iteration.py).  Saved by the testing build when a solve returns; CUP3D_ESTATE before one has.
+ * The Helmholtz solves leave the same record: after cup3d_diffusion_solve, or after the last of the three solves of
+ * cup3d_advect_diffuse_implicit (component 2), the read-outs describe that solve (tests/test_gpu_helmholtz_iteration.py).  Every
+ * iteration of such a solve is host-driven, so t = A what is live and q.y, y.y are reported after each; io[11] reads 2147483647
+ * (DiffusionSolver::solve has no cap on its restarts, whatever cup3d_poisson_params::max_restarts says).
  *
  * cup3d_debug_solver_vector: one work vector, slot order, nblocks*512 doubles (host memory).  `which` counts the logical vectors in
  * the order of poisson_vector.hpp: 0 phat, 1 rhat, 2 shat, 3 what, 4 zhat, 5 qhat, 6 s, 7 w, 8 z, 9 t, 10 v, 11 q, 12 r, 13 y, 14 x, 15 r0,

@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 
 import cup3d_amd as cu
+import helmholtz_cases as H
+import implicit_step_restatement as ST
 import multigrid_cases as K
 import oracle_lib as O
 from cup3d_amd.capi import check, lib
@@ -782,3 +784,202 @@ def test_grad_chi_on_tmp_over_ranks_equals_the_reference(golden_dir, name, nrank
         del sims, views
     for tag in ("", "_capped"):
         assert np.array_equal(got[tag], z[name + "_tmpV" + tag]), (name, tag)
+
+
+# ------------------------------------------------------------------ implicit diffusion over ranks (AdvectionDiffusionImplicit, main.cpp:10030-10118)
+# KernelAdvect, KernelDiffusionRHS and KernelLHSDiffusion with their inner-then-boundary split -- the Helmholtz tiles' per-component
+# domain-face rule has to survive into the second ghost-fill pass (halo_finish restores scalar_bc_dir) -- the k_imp_* passes on rank views,
+# and DiffusionSolver::solve with all-reduced totals.  Stencils and the step without iterations: BIT-EXACT against the one-rank oracle /
+# tests/implicit_step_restatement.py; solves: the solver-tolerance bounds of tests/test_gpu_amr.py::test_implicit_diffusion_solver (the
+# ranks sum the dot products in another association).
+IMP_DT, IMP_NU, IMP_UINF = 0.05, 2.0, (0.1, -0.2, 0.3)
+
+
+class _Spread:
+    """One mesh on `nranks` thread ranks (inside a VirtualComm): a uniform grid cut by the library, or a multi-level mesh by rank views of
+    the ownership `kind`.  take(r, a): rank r's blocks of an array in the one-rank slot order; gather(parts): back into that order."""
+
+    def __init__(self, name, nranks, kind="ranges", seed=0, **sim_kw):
+        self.nranks = nranks
+        if name == "uniform222":
+            bpd, lmax, level, bc = (2, 2, 2), 2, 1, ("wall", "periodic", "freespace")
+            lv, zs = H.uniform_leaves(bpd, lmax, level)
+            self.og = O.OracleGrid(bpd, lmax, level, EXT, bc)
+        else:
+            bpd, lmax, bc, lv, zs = _mesh_case(name)
+            level, self.og = 0, None
+        self.m = m = O.OracleMesh(bpd, lmax, EXT, bc, lv, zs)
+        self.h = np.array([m.h(b) for b in range(m.nb)])
+        kw = dict(bpdx=bpd[0], bpdy=bpd[1], bpdz=bpd[2], levelMax=lmax, levelStart=level, extent=EXT, BC_x=bc[0], BC_y=bc[1], BC_z=bc[2],
+                  nu=IMP_NU, uinf=IMP_UINF, **sim_kw)
+        if self.og is not None:
+            assert np.array_equal(self.og.tables[:, :5], m.tables[:, :5])
+            self.views = None
+            self.sims = [cu.SimulationData(rank=r, nranks=nranks, **kw) for r in range(nranks)]
+        else:
+            mesh = cu.operators.Grid(bpd, lmax, 0, EXT, bc, leaves=(lv, zs))
+            assert np.array_equal(mesh.tables, m.tables)
+            owner = _owners(m.nb, nranks, kind, seed=seed)
+            self.views = [mesh.rank_view(owner, r, nranks) for r in range(nranks)]
+            self.sims = [cu.SimulationData(view=v, **kw) for v in self.views]
+            self.mine = [v.global_slot[:v.nlocal] for v in self.views]
+            assert sum(v.nghost for v in self.views) > 0
+        assert sum(s.nblocks for s in self.sims) == m.nb
+        rng = np.random.default_rng(6)
+        self.vel, self.pres, self.rhs = 0.5 * rng.uniform(-1, 1, (m.nb, 8, 8, 8, 3)), rng.uniform(-1, 1, (m.nb, 8, 8, 8)), rng.uniform(-1, 1, (m.nb, 8, 8, 8))
+
+    def take(self, r, a):
+        return self.sims[r].grid.to_blocks(self.og.to_global(a)) if self.og is not None else a[self.mine[r]]
+
+    def gather(self, parts):
+        if self.og is None:
+            out = np.zeros((self.m.nb,) + parts[0].shape[1:])
+            for r in range(self.nranks):
+                out[self.mine[r]] = parts[r]
+            return out
+        NX, NY, NZ = self.og.ncell
+        g = np.zeros((NZ, NY, NX) + parts[0].shape[4:])
+        for r, s in enumerate(self.sims):
+            s.grid.scatter_to_global(parts[r], g)
+        return self.og.to_blocks(g)
+
+    def not_inner(self, r):
+        """one-rank slots of rank r's blocks that wait for the ghost exchange (filled in the second pass)"""
+        v = self.views[r]
+        inner = np.zeros(max(v.ninner, 1), dtype=np.int32)
+        check(lib().cup3d_debug_grid_inner_blocks(v.handle, inner.ctypes.data_as(C.c_void_p)))
+        return self.mine[r][np.setdiff1d(np.arange(v.nlocal), inner[:v.ninner])]
+
+    def run(self, fn):
+        """fn(rank, sim) -> dict of arrays; returns the gathered dict"""
+        out = [None] * self.nranks
+
+        def rank(r):
+            out[r] = fn(r, self.sims[r])
+
+        run_ranks(rank, self.nranks)
+        return {k: (self.gather([o[k] for o in out]) if isinstance(out[0][k], np.ndarray) else [o[k] for o in out]) for k in out[0]}
+
+    def close(self):
+        del self.sims, self.views
+
+
+def _implicit_stencils(S_):
+    def fn(r, s):
+        got = {}
+        s.upload("vel", S_.take(r, S_.vel))
+        check(lib().cup3d_advect_implicit(s.handle, IMP_DT, IMP_NU, np.array(IMP_UINF)))
+        got["adv_vel"], got["adv_tmpV"] = s.download("vel"), s.download("tmpV")
+        s.upload("vel", S_.take(r, S_.vel))
+        check(lib().cup3d_diffusion_rhs(s.handle))
+        got["rhs"] = s.download("tmpV")
+        for d in range(3):
+            s.upload("pres", S_.take(r, S_.pres))
+            check(lib().cup3d_diffusion_lhs(s.handle, d, IMP_DT, IMP_NU))
+            got[f"lhs{d}"] = s.download("lhs")
+        return got
+
+    got = S_.run(fn)
+    m = S_.m
+    v, t = m.advect_implicit(S_.vel, IMP_DT, IMP_NU, IMP_UINF, False)
+    ref = dict(adv_vel=v, adv_tmpV=t, rhs=m.diffusion_rhs(S_.vel), **{f"lhs{d}": m.diff_lhs(S_.pres, d, IMP_DT, IMP_NU) for d in range(3)})
+    return got, ref
+
+
+@pytest.mark.parametrize("nranks,kind", [(2, "ranges"), (3, "scattered"), (5, "ranges")])
+@pytest.mark.parametrize("name", ["l012_wall", "l012_periodic", "l012_box322"])
+def test_implicit_diffusion_stencils_on_a_multilevel_mesh_over_ranks(name, nranks, kind):
+    with VirtualComm(nranks):
+        S_ = _Spread(name, nranks, kind, seed=len(name))
+        got, ref = _implicit_stencils(S_)
+        if name == "l012_wall":
+            # the face rule of the component must matter on a block of the SECOND pass (the blocks that wait for the ghost exchange: filled
+            # after halo_begin has returned and scalar_bc_dir was reset): else a lost hand-over of the direction would go unseen
+            differs = np.where((ref["lhs0"] != ref["lhs1"]).reshape(S_.m.nb, -1).any(axis=1))[0]
+            waiting = np.concatenate([S_.not_inner(r) for r in range(nranks)])
+            assert len(np.intersect1d(differs, waiting)) > 0, (differs, waiting)
+        S_.close()
+    for k in ref:
+        assert np.array_equal(got[k], ref[k]), (name, nranks, kind, k, np.abs(got[k] - ref[k]).max())
+
+
+@pytest.mark.parametrize("nranks", [2, 3, 8])
+def test_implicit_diffusion_stencils_on_a_uniform_grid_over_ranks(nranks):
+    """(2,2,2) level 1, wall / periodic / freespace: face slabs instead of ghost blocks"""
+    with VirtualComm(nranks):
+        S_ = _Spread("uniform222", nranks)
+        got, ref = _implicit_stencils(S_)
+        S_.close()
+    assert not np.array_equal(ref["lhs0"], ref["lhs2"])
+    for k in ref:
+        assert np.array_equal(got[k], ref[k]), (nranks, k, np.abs(got[k] - ref[k]).max())
+
+
+def _implicit_step(S_, tol, tol_rel, max_iter=None):
+    def fn(r, s):
+        s.upload("vel", S_.take(r, S_.vel))
+        s.upload("pres", S_.take(r, S_.pres))
+        p = cu.capi.PoissonParams()
+        lib().cup3d_poisson_default_params(C.byref(p))
+        p.tol, p.tol_rel = tol, tol_rel
+        if max_iter is not None:
+            p.max_iter = max_iter
+        res = (cu.capi.PoissonResult * 3)()
+        check(lib().cup3d_advect_diffuse_implicit(s.handle, IMP_DT, IMP_NU, np.array(IMP_UINF), C.byref(p), res))
+        return dict(vel=s.download("vel"), tmpV=s.download("tmpV"), pres=s.download("pres"), counts=tuple((res[i].iterations, res[i].restarts) for i in range(3)))
+
+    return S_.run(fn)
+
+
+@pytest.mark.parametrize("name,nranks,kind", [("uniform222", 3, "ranges"), ("l012_wall", 3, "scattered")])
+def test_implicit_step_without_iterations_over_ranks_is_the_restated_step(name, nranks, kind):
+    """max_iter = 0: every solve returns its zero guess, nothing that depends on the partition enters -- vel, tmpV and pres are the bits of
+    tests/implicit_step_restatement.py (k_imp_* on rank views: per-block h of the local slots, component planes of the local blocks)"""
+    with VirtualComm(nranks):
+        S_ = _Spread(name, nranks, kind, seed=7)
+        got = _implicit_step(S_, 0.0, 0.0, max_iter=0)
+        S_.close()
+    m = S_.m
+    want = ST.euler(S_.vel, S_.pres, S_.h, IMP_DT, IMP_NU, lambda v: m.advect_implicit(v, IMP_DT, IMP_NU, IMP_UINF, False), m.diffusion_rhs,
+                    lambda rhs, x0, direction: x0.copy())
+    assert all(c == ((0, 0),) * 3 for c in got["counts"])
+    for k in ("tmpV", "vel", "pres"):
+        assert np.array_equal(got[k].view(np.int64), want[k].view(np.int64)), (name, k, np.abs(got[k] - want[k]).max())
+
+
+@pytest.mark.parametrize("name,nranks,kind", [("uniform222", 2, "ranges"), ("uniform222", 3, "ranges"), ("l012_wall", 2, "ranges")])
+def test_implicit_step_at_tight_tolerance_over_ranks(name, nranks, kind):
+    with VirtualComm(nranks):
+        S_ = _Spread(name, nranks, kind, seed=7)
+        got = _implicit_step(S_, 1e-12, 1e-11)
+        S_.close()
+    v, its = S_.m.advdiff_implicit(S_.vel, S_.pres, IMP_DT, IMP_NU, IMP_UINF, False, 1e-12, 1e-11)
+    assert len(set(got["counts"])) == 1, got["counts"]          # every rank took the same path through the three solves
+    assert all(c[0] > 3 for c in got["counts"][0])
+    assert np.array_equal(got["pres"], S_.pres)
+    change = np.abs(v - S_.vel).max()
+    assert change > 1e-3
+    assert np.abs(got["vel"] - v).max() <= 1e-6 * change
+
+
+def test_diffusion_solve_at_default_tolerance_over_three_ranks():
+    """the iterate the sharded Helmholtz solve returns satisfies the reference's stopping rule under the ORACLE's operator on the gathered field"""
+    nranks, d = 3, 1
+    with VirtualComm(nranks):
+        S_ = _Spread("uniform222", nranks)
+
+        def fn(r, s):
+            s.upload("lhs", S_.take(r, S_.rhs))
+            s.upload("pres", S_.take(r, S_.pres))
+            p, res = cu.capi.PoissonParams(), cu.capi.PoissonResult()
+            lib().cup3d_poisson_default_params(C.byref(p))
+            check(lib().cup3d_diffusion_solve(s.handle, d, IMP_DT, IMP_NU, C.byref(p), C.byref(res)))
+            return dict(x=s.download("pres"), its=res.iterations)
+
+        got = S_.run(fn)
+        S_.close()
+    m = S_.m
+    res = np.linalg.norm((S_.rhs - m.diff_lhs(got["x"], d, IMP_DT, IMP_NU)).ravel())
+    res0 = np.linalg.norm((S_.rhs - m.diff_lhs(S_.pres, d, IMP_DT, IMP_NU)).ravel())
+    assert len(set(got["its"])) == 1 and got["its"][0] >= 2
+    assert res <= 1.05 * max(1e-6, 1e-4 * res0), (res, res0)

@@ -272,6 +272,11 @@ __global__ void __launch_bounds__(256) k_pack_blocks(const double *__restrict__ 
   double *dst = out + (size_t)blockIdx.x * nc * 512;
   for (int i = threadIdx.x; i < nc * 512; i += 256) dst[i] = src[i];
 }
+__global__ void __launch_bounds__(256) k_unpack_blocks(const double *__restrict__ in, const int32_t *__restrict__ slots, int nc, double *__restrict__ field) {
+  const double *src = in + (size_t)blockIdx.x * nc * 512;
+  double *dst = field + (size_t)slots[blockIdx.x] * nc * 512;
+  for (int i = threadIdx.x; i < nc * 512; i += 256) dst[i] = src[i];
+}
 __global__ void __launch_bounds__(64) k_pack_flux(const double *__restrict__ flux, const int32_t *__restrict__ faces, int nfc, double *__restrict__ out) {
   const double *src = flux + (size_t)faces[blockIdx.x] * nfc * 64;
   double *dst = out + (size_t)blockIdx.x * nfc * 64;
@@ -310,8 +315,18 @@ __global__ void __launch_bounds__(256) k_poison(double *__restrict__ p, size_t n
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = __builtin_nan("");
 }
 
-// the same three kernels for a caller in another file (cup3d_sim_labs_over_ranks, amr.hip: boxes asked for per call, a pool of ghost
-// blocks instead of the ghost slots of a field): n blocks of `nc` components each, on stream st
+// the same kernels for a caller in another file: n blocks of `nc` components each, on stream st.  Whole blocks (ViewField, sim.hpp; adapt.hip) ...
+int launch_pack_blocks(const double *field, const int32_t *slots, int nc, double *out, unsigned n, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_pack_blocks, dim3(n), dim3(256), 0, st, field, slots, nc, out);
+  CUP3D_HIP(hipGetLastError());
+  return CUP3D_OK;
+}
+int launch_unpack_blocks(const double *in, const int32_t *slots, int nc, double *field, unsigned n, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_unpack_blocks, dim3(n), dim3(256), 0, st, in, slots, nc, field);
+  CUP3D_HIP(hipGetLastError());
+  return CUP3D_OK;
+}
+// ... and sub-boxes (cup3d_sim_labs_over_ranks, labs.hip: boxes asked for per call, a pool of ghost blocks instead of a field's ghost slots)
 int launch_pack_boxes(const double *field, const int32_t *slots, const unsigned char *box, const long long *off, int nc, double *out, unsigned n, hipStream_t st) {
   if (n) hipLaunchKernelGGL(k_pack_boxes, dim3(n), dim3(256), 0, st, field, slots, box, off, nc, out);
   CUP3D_HIP(hipGetLastError());

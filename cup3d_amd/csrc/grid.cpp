@@ -261,8 +261,8 @@ Grid::Grid(const Grid &p, int)
 // The cells of REMOTE blocks that the star-stencil consumers of rank r's blocks read, for a stencil of width W (1 or 3), as one bounding
 // box per remote block (global slot -> lo[3], hi[3]).  Each consumer's index arithmetic is replayed here exactly:
 //   * a stencil kernel's tile: the W layers of a same-level face neighbour behind the shared face;
-//   * k_ghost_restrict (amr.hip): the 2W layers of the four finer leaves behind a face;
-//   * k_ghost_prolong (amr.hip): the coarse shadow patch of W layers x 6 x 6 behind a face whose neighbour is coarser -- cells of coarser
+//   * ghost_restrict_face (k_ghosts, amr.hip): the 2W layers of the four finer leaves behind a face;
+//   * ghost_prolong_face (k_ghosts, amr.hip): the coarse shadow patch of W layers x 6 x 6 behind a face whose neighbour is coarser -- cells of coarser
 //     leaves, and 2x2x2 averages over cells of same-level edge / corner neighbours; domain faces clamp the patch as the kernel does.
 namespace {
 struct CellBox { uint8_t lo[3] = {8, 8, 8}, hi[3] = {0, 0, 0}; };

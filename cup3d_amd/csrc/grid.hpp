@@ -151,7 +151,7 @@ struct Grid {
   // (refine_1 / RefineBlocks) averages down; the star-shaped stencils of the time step never read them
   std::unique_ptr<Grid> rank_view(const int32_t *owner, int rank, int nranks, bool tensorial = false) const;
   // Tensorial rank views: the cells of GHOST blocks that the ghosted tiles [-w, w+1)^3 of the local blocks `slots` (nullptr: all n_local
-  // of them; repeats allowed) read -- k_labs' index arithmetic (amr.hip) replayed on the host, as star_boxes replays the star consumers:
+  // of them; repeats allowed) read -- k_labs' index arithmetic (labs_phases.hpp) replayed on the host, as star_boxes replays the star consumers:
   // the w layers of a same-level neighbour (one, two or three axes off centre), the 2w layers of a finer leaf that AverageDown reads,
   // and -- for a block with a coarser neighbour anywhere -- what its coarse shadow tile [-3, 7)^3 takes: cells of coarser leaves, 2x2x2
   // averages over same-level neighbours.  box[nghost][6]: the union over the tiles as one bounding box per ghost block, lo x, y, z,

@@ -1,4 +1,4 @@
-// The SET-UP of a kernel that assembles ghosted block tiles (amr.hip: k_labs<W>, k_labs_view<W>, k_refine<NC>, k_grad_chi), included as
+// The SET-UP of a kernel that assembles ghosted block tiles (k_labs<W>, k_labs_view<W>: labs.hip; k_refine<NC>: adapt.hip; k_grad_chi: grad_chi.hip), included as
 // text at the top of the kernel's body; labs_phases.hpp, included after it, assembles one component.  (A __device__ function template
 // on the block source was the first form; inlined, it compiled k_labs to other register figures than the ones
 // tests/test_labs_kernel_resources.py holds it to -- 5 and 4 scalar registers parked in VGPR lanes at w = 2 and 3 instead of 2 --

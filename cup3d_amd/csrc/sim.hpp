@@ -10,8 +10,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -132,8 +135,8 @@ struct Sim {
   Pinned<unsigned> h_early_fail;
   unsigned *h_early_fail_dev = nullptr;  // pinned: a bounded device-side wait of the early all-reduce gave up
   void *mg = nullptr;              // level hierarchy of the multigrid preconditioner (multigrid.hip), built on first use
-  struct LabTables *labs = nullptr;  // tables and staging buffer of cup3d_sim_labs (amr.hip), built on first use
-  struct LabsView *labs_view = nullptr;  // cup3d_sim_labs_over_ranks: the rank's tensorial view, its tables, the ghost pool (amr.hip)
+  struct LabTables *labs = nullptr;  // tables and staging buffer of cup3d_sim_labs (labs.hip), built on first use
+  struct LabsView *labs_view = nullptr;  // cup3d_sim_labs_over_ranks: the rank's tensorial view, its tables, the ghost pool (labs.hip)
   struct ForcesScratch *forces = nullptr;  // cup3d_compute_forces: tile scratch and staged surface arrays, grow-only (obstacles_forces.hip)
   // what the last successful cup3d_create_obstacles left on the device, per obstacle of that call: slots, geom, sdfLab, chi and the
   // corrected udef -- what cup3d_prevent_colliding_obstacles and the resident operators (cup3d_*_resident) read, with the latter's plan
@@ -219,11 +222,57 @@ int view_exchange_flux(Sim *s, int nfc);
 int view_exchange_blocks(Sim *s, double *field, int nc, int w);  // w: width of the star stencil that will read them (1 or 3)
 // generic exchange of `per`-double items between ranks (own rank included), peer-major buffers; compute stream
 int exchange_items(Sim *s, const double *sendbuf, const std::vector<int64_t> &send_count, double *recvbuf, const std::vector<int64_t> &recv_count, size_t per);
-// the sub-box pack / unpack kernels of the ghost-block exchange and the NaN fill of "poison_ghosts" for a caller outside comm.hip:
-// block i of `slots` contributes the cells of box[i] at offset off[i] * nc of the message; they arrive in box[i] of block row i
+// the pack / unpack kernels of the ghost-block exchange and the NaN fill of "poison_ghosts" for a caller outside comm.hip.  Whole blocks ...
+int launch_pack_blocks(const double *field, const int32_t *slots, int nc, double *out, unsigned n, hipStream_t st);
+int launch_unpack_blocks(const double *in, const int32_t *slots, int nc, double *field, unsigned n, hipStream_t st);
+// ... sub-boxes: block i of `slots` contributes the cells of box[i] at offset off[i] * nc of the message; they arrive in box[i] of block row i
 int launch_pack_boxes(const double *field, const int32_t *slots, const unsigned char *box, const long long *off, int nc, double *out, unsigned n, hipStream_t st);
 int launch_unpack_boxes(double *blocks, const unsigned char *box, const long long *off, int nc, const double *in, unsigned n, hipStream_t st);
 int launch_nan_fill(double *p, size_t n_doubles, hipStream_t st);
+// The grid of a sim as a mesh object: a uniform grid is read as the one-level mesh it is (Grid::as_mesh), which lives as long as this
+// does; a mesh is itself.  nullptr: the error text is set ("<who>: ..."), the caller returns CUP3D_EINVAL.
+struct MeshOf {
+  std::unique_ptr<Grid> tmp;
+  const Grid *get(const Grid *g, const char *who) {
+    try {
+      if (!g->multilevel) { tmp = g->as_mesh(); g = tmp.get(); }
+    } catch (const std::exception &e) { set_error("%s: %s", who, e.what()); return nullptr; }
+    return g;
+  }
+};
+// A field of a sim on the rank's TENSORIAL view of a mesh spread over ranks: F[slot of tv][nc][512], the local blocks copied, the ghost blocks
+// fetched whole from their owners.  Two steps around the caller's agree(): stage() is what one rank can get wrong alone, exchange() the collective.
+struct ViewField {
+  std::unique_ptr<Grid> tv;
+  Dev<double> F, pack;
+  Dev<int32_t> d_send;
+  size_t per = 0;  // doubles per block
+  // the view of (mesh, owner) for the rank of `s`, whose `field` (nc components) holds its local blocks (`not_mine`: the error text where
+  // not); `plan`: what else of the caller's can throw before anything is allocated; then buffers, local blocks and the packed send list
+  template <class Plan>
+  int stage(const Grid *mesh, const int32_t *owner, const Sim *s, const double *field, int nc, const char *who, const char *not_mine, Plan &&plan) {
+    try {
+      tv = mesh->rank_view(owner, s->grid->rank, s->grid->nranks, /*tensorial=*/true);
+      if (tv->n_local != s->nb) throw std::invalid_argument(not_mine);
+      plan();
+    } catch (const std::exception &e) {
+      set_error("%s: %s", who, e.what());
+      return CUP3D_EINVAL;
+    }
+    per = (size_t)nc * 512;
+    int rc;
+    if ((rc = F.alloc(tv->Z.size() * per)) || (rc = pack.alloc(std::max<size_t>(tv->send_blocks.size(), 1) * per)) || (rc = d_send.upload(tv->send_blocks, stream(), IfEmpty::null))) return rc;
+    CUP3D_HIP(hipMemcpyAsync(F, field, (size_t)s->nb * per * sizeof(double), hipMemcpyDeviceToDevice, stream()));
+    return launch_pack_blocks(F, d_send, nc, pack, (unsigned)tv->send_blocks.size(), stream());
+  }
+  // the ghost blocks arrive behind the local ones; synchronises
+  int exchange(Sim *s) {
+    if (int rc = exchange_items(s, pack, tv->send_block_count, F + (size_t)tv->n_local * per, tv->recv_block_count, per)) return rc;
+    CUP3D_HIP(hipStreamSynchronize(stream()));
+    return CUP3D_OK;
+  }
+};
+
 void vcomm_register(Sim *s);    // in-process test communicator (comm.hip)
 void vcomm_unregister(Sim *s);
 
@@ -241,7 +290,7 @@ int launch_mean_total(Sim *s);  // total of the block sums in d_partials' tail -
 // block_solver 5: one multigrid V-cycle from a zero guess as M^-1 (multigrid.hip; an alternative, not the reference's algorithm)
 int mg_vcycle(Sim *s, const double *in, double *out);
 void mg_destroy(Sim *s);
-void labs_destroy(Sim *s);  // what cup3d_sim_labs and cup3d_sim_labs_over_ranks built on first use (amr.hip)
+void labs_destroy(Sim *s);  // what cup3d_sim_labs and cup3d_sim_labs_over_ranks built on first use (labs.hip)
 void forces_destroy(Sim *s);  // the scratch of cup3d_compute_forces (obstacles_forces.hip)
 void retained_destroy(Sim *s);  // the obstacle blocks cup3d_create_obstacles keeps (obstacles_create.hip)
 // implicit diffusion (DiffusionSolver, main.cpp:6719-7147): Helmholtz operator of velocity component `direction`

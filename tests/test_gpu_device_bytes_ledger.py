@@ -115,7 +115,7 @@ def measure_amr():
 
 def measure_two_ranks():
     """the uniform grid as a share of two thread ranks: [rank 0, rank 1] per checkpoint.  No labs_host / labs_device here: cup3d_sim_labs
-    refuses a sim that holds one rank's share (labs_check, csrc/amr.hip); its tiles come from cup3d_sim_labs_over_ranks."""
+    refuses a sim that holds one rank's share (labs_check, csrc/labs.hip); its tiles come from cup3d_sim_labs_over_ranks."""
     n = 2
     mesh, owner = cu.operators.uniform_share_mesh((1, 1, 1), 3, 2, EXT, BC, n)
     out = {}

@@ -1,4 +1,4 @@
-"""cup3d_sim_labs / cup3d_sim_labs_device: ghosted block tiles of any stencil box, built on the device (k_labs, csrc/amr.hip), against the
+"""cup3d_sim_labs / cup3d_sim_labs_device: ghosted block tiles of any stencil box, built on the device (k_labs, csrc/labs.hip), against the
 CPU oracle's restatement of BlockLab::load + post_load (orc_mesh_labs, pinned to the compiled reference for these boxes by
 test_oracle_amr.py and test_oracle_wide_labs.py) and against the reference's own tiles.
 

@@ -1,5 +1,5 @@
 """cup3d_sim_labs_over_ranks / cup3d_sim_labs_over_ranks_device: ghosted block tiles on a mesh spread over ranks (k_labs_view and the
-request / data exchange of csrc/amr.hip, the request plan of Grid::lab_boxes), on ONE GPU: the ranks are host threads of this process
+request / data exchange of csrc/labs.hip, the request plan of Grid::lab_boxes), on ONE GPU: the ranks are host threads of this process
 and the in-process communicator (cup3d_debug_virtual_comm) stands in for RCCL, as in test_gpu_multirank.py.  MI355X only (-m gpu).
 
 A tile does not depend on how the mesh is partitioned: the expected tiles are the CPU oracle's (OracleMesh.labs, pinned to the compiled

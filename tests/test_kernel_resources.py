@@ -29,6 +29,12 @@ def test_every_translation_unit_carries_gfx950_code(release):
     triples = {t for t, _ in KR.code_objects(RELEASE)}
     assert triples and all("gfx950" in t for t in triples), triples   # one architecture, no second code path
     assert len(release) > 90
+    # k_pack_blocks / k_unpack_blocks live in comm.hip alone; other files reach them through launch_pack_blocks / launch_unpack_blocks
+    # (sim.hpp).  The ROWS of each library are counted: a dict by name, like `release`, would hide a second copy in another translation unit
+    for path in (RELEASE, TESTING):
+        names = [r["kernel"] for r in KR.kernels(path)]
+        for k in ("k_pack_blocks", "k_unpack_blocks"):
+            assert names.count(k) == 1, (path, k, names.count(k))
 
 
 def test_fused_solver_kernels(release):

@@ -1,4 +1,4 @@
-"""What the compiler made of k_labs, the ghosted-tile kernel of cup3d_sim_labs (csrc/amr.hip), read from the code objects of both built
+"""What the compiler made of k_labs, the ghosted-tile kernel of cup3d_sim_labs (csrc/labs.hip), read from the code objects of both built
 libraries (no GPU): nothing in scratch, no vector register spilled, and at most 80 KB of LDS per workgroup, so that two workgroups fit
 the 160 KB of a compute unit (the widest tile, 16^3 fine cells plus the 10^3 coarse shadow tile of one component, takes 40 768 B).
 

@@ -1,4 +1,4 @@
-"""What the compiler made of k_labs_view, the ghosted-tile kernel of cup3d_sim_labs_over_ranks (csrc/amr.hip: the phases of k_labs read
+"""What the compiler made of k_labs_view, the ghosted-tile kernel of cup3d_sim_labs_over_ranks (csrc/labs.hip: the phases of k_labs read
 through a rank's tensorial view, local blocks from the field array and ghost blocks from the call's pool), read from the code objects
 of both built libraries (no GPU): one instantiation per box width, nothing in scratch, no vector register spilled, one component's
 fine tile plus the 10^3 coarse shadow tile in LDS and never more than 80 KB, so that two workgroups fit a compute unit.

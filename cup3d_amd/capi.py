@@ -181,6 +181,7 @@ SIGNATURES = {
     "cup3d_diffusion_rhs": (C.c_int, [_vp]),
     "cup3d_diffusion_lhs": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
     "cup3d_diffusion_preconditioner": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "cup3d_diffusion_set_block_solver": (C.c_int, [_vp, C.c_int]),
     "cup3d_diffusion_solve": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.POINTER(PoissonParams), C.POINTER(PoissonResult)]),
     "cup3d_penalization": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Obstacle)]),
     "cup3d_update_tmpv": (C.c_int, [_vp, C.c_int, C.POINTER(Obstacle)]),

@@ -60,7 +60,9 @@ static cup3d_poisson_params diffusion_params(const cup3d_poisson_params *pp) {
   cup3d_poisson_params P;
   cup3d_poisson_default_params(&P);  // 1e-6 / 1e-4 are also sim.DiffusionErrorTol / DiffusionErrorTolRel (15369-15370)
   if (pp) P = *pp;
-  if (P.block_solver != 2) P.block_solver = 0;  // block CG only (2 = reference association): the direct block solve is written for the Poisson coefficient
+  // params.block_solver only chooses the association of the block CG (2 = the reference's); whether the block solve is the CG or the
+  // direct solve with the shifted eigenvalues is a setting of the sim (cup3d_diffusion_set_block_solver), read by launch_precond_diffusion
+  if (P.block_solver != 2) P.block_solver = 0;
   return P;
 }
 
@@ -90,6 +92,16 @@ int cup3d_diffusion_preconditioner(cup3d_sim_t *h, double dt, double nu) {
   if (!h) return CUP3D_EINVAL;
   Sim *s = reinterpret_cast<Sim *>(h);
   return launch_precond_diffusion(s, s->pres, s->pres, HelmholtzOp{0, dt, nu});  // in place, as cup3d_preconditioner
+}
+
+int cup3d_diffusion_set_block_solver(cup3d_sim_t *h, int block_solver) {
+  if (!h) return CUP3D_EINVAL;
+  if (block_solver != 0 && block_solver != 1) {
+    set_error("cup3d_diffusion_set_block_solver: block_solver %d (0 = block CG, 1 = direct solve)", block_solver);
+    return CUP3D_EINVAL;
+  }
+  reinterpret_cast<Sim *>(h)->diffusion_block_solver = block_solver;
+  return CUP3D_OK;
 }
 
 int cup3d_diffusion_solve(cup3d_sim_t *h, int direction, double dt, double nu, const cup3d_poisson_params *pp, cup3d_poisson_result *r) {

@@ -833,3 +833,20 @@ int cup3d_pressure_project(cup3d_sim_t *h, double dt, int step, const cup3d_pois
 }
 
 }  // extern "C"
+
+namespace cup3d {
+
+// The direct block solve of the implicit diffusion (launch_precond_diffusion with cup3d_diffusion_set_block_solver(sim, 1)).  LAST in this
+// translation unit on purpose: it holds the only use of k_precond_fdm_helm, which puts that kernel behind every other one (see there).
+static int launch_precond_fdm_helm(Sim *s, const double *in, double *out, const HelmholtzOp &op) {
+  GridDev g = s->gdev();
+  int rc = fdm_setup();
+  if (rc) return rc;
+  ProfileScope ps("diffusion_block_fdm");
+  hipLaunchKernelGGL(k_precond_fdm_helm<>, dim3(launch_groups(g)), dim3(64), 0, stream(), g, in, out, op.nu, op.dt);
+  CUP3D_HIP(hipGetLastError());
+  s->sums_of = nullptr;
+  return CUP3D_OK;
+}
+
+}  // namespace cup3d

@@ -334,7 +334,13 @@ __global__ void __launch_bounds__(64) k_precond_pair(GridDev g, int pchunk, cons
 // lane against ~124 per CG ITERATION.  Its result differs from the reference's CG result by
 // the CG's own truncation error (<= cond * 1e-7), i.e. it is the same preconditioner
 // evaluated more accurately; selected with cup3d_poisson_params.block_solver = 1.
+// HELM: the block operator of the implicit diffusion, sum6(z) + (-6 - h^2/nu/dt) z (diffusion_kernels::getZImplParallel, 10534-10579), has
+// the same eigenvectors and the eigenvalues lam_i + lam_j + lam_k - h^2/nu/dt.  The shift differs per block (h) and per call (dt, nu), so
+// there is no table of reciprocals: every lane forms its eight divisors from the 1-D eigenvalues in cLam and divides (IEEE divisions: the
+// solve stays a sequence of IEEE operations that is linear in r, so z(2^k r) == 2^k z(r) bit for bit).  Selected per sim with
+// cup3d_diffusion_set_block_solver(sim, 1).
 __constant__ double cQ[8][4];
+__constant__ double cLam[8];      // lam_k = 2 cos(pi (k+1)/9) - 2 (HELM)
 static double *g_invD = nullptr;  // [ky][kz][kx] = 1 / (lam_kx + lam_ky + lam_kz)
 
 __device__ __forceinline__ void sine_transform8(const double (&v)[8], double (&o)[8]) {
@@ -350,15 +356,16 @@ __device__ __forceinline__ void sine_transform8(const double (&v)[8], double (&o
 constexpr int kFdmLds = 64 * 9;  // transposes; pitch 9 doubles keeps every ds_read/write_b64 conflict-free
 // the direct solve of one block by its wavefront: v[z] = (right-hand side / h) of cell (x = lane & 7, y = lane >> 3, z) on entry;
 // out receives M^-1, block_sums[slot] (if any) sum(z h^3).  T: kFdmLds doubles of LDS nobody else is using.
-template <bool AG = false>
+// HELM: the eigenvalues are shifted by -shift (= h^2/nu/dt of this block) and invD is not read.
+template <bool AG = false, bool HELM = false>
 __device__ __forceinline__ void fdm_block(const GridDev &g, int slot, double (&v)[8], double *__restrict__ out, const double *__restrict__ invD,
-                                          double *__restrict__ block_sums, double *T) {
+                                          double *__restrict__ block_sums, double *T, double shift = 0.0) {
   const int l = threadIdx.x, lo = l & 7, hi = l >> 3;
   double w[8], scale[8];
   double rr = 0;
 #pragma unroll
   for (int z = 0; z < 8; ++z) {
-    scale[z] = invD[z * 64 + l];
+    if constexpr (!HELM) scale[z] = invD[z * 64 + l];
     rr = __builtin_fma(v[z], v[z], rr);
   }
   rr = wave_sum(rr);
@@ -379,8 +386,14 @@ __device__ __forceinline__ void fdm_block(const GridDev &g, int slot, double (&v
   for (int k = 0; k < 8; ++k) v[k] = T[l * 9 + k];  // lane (kx=lo, kz=hi), register y
   __syncthreads();
   sine_transform8(v, w);  // register ky
+  if constexpr (HELM) {
+    const double lxz = cLam[lo] + cLam[hi];  // this lane's kx and kz; cLam[k] below is the same for every lane
 #pragma unroll
-  for (int k = 0; k < 8; ++k) w[k] *= scale[k];
+    for (int k = 0; k < 8; ++k) w[k] = w[k] / ((lxz + cLam[k]) - shift);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] *= scale[k];
+  }
   // inverse: y, x, z
   sine_transform8(w, v);  // register y, lane (kx, kz)
 #pragma unroll
@@ -421,6 +434,24 @@ __global__ void __launch_bounds__(64) k_precond_fdm(GridDev g, const double *in,
   for (int z = 0; z < 8; ++z) v[z] = invh * in[(size_t)slot * 512 + z * 64 + l];
   fdm_block(g, slot, v, out, invD, block_sums, T);
 }
+// the same for the Helmholtz block operator of the implicit diffusion; the shift as cg_block<.., HELM> evaluates it.
+// A template for its PLACE in the code object alone: the compiler emits the plain kernels in the order of their definitions and the
+// instantiations behind them in the order of their first use, and this one's only use is the last thing in poisson.hip
+// (launch_precond_fdm_helm), so it lands behind every other kernel and none of them moves.  Emitted where it is written, in front of the loop
+// kernels, it shifted them by 4864 bytes, and bicgstab_loop1_cg (k_loop1_cg_w5, the same instructions) ran 1.4 % slower at 512^3: 3.922-3.965
+// against 3.865-3.869 ms, release libraries alternating x3 on one box (profiles/helmholtz_direct_block_solve/).
+template <int = 0>
+__global__ void __launch_bounds__(64) k_precond_fdm_helm(GridDev g, const double *in, double *out, double nu, double dt) {
+  __shared__ double T[kFdmLds];
+  const int slot = block_slot(g);
+  if (slot < 0) return;
+  const int l = threadIdx.x;
+  const double hq = block_h(g, slot), invh = 1 / hq;
+  double v[8];
+#pragma unroll
+  for (int z = 0; z < 8; ++z) v[z] = invh * in[(size_t)slot * 512 + z * 64 + l];
+  fdm_block<false, true>(g, slot, v, out, nullptr, nullptr, T, hq * hq / nu / dt);
+}
 
 #ifdef CUP3D_TESTING
 // TEST SUPPORT: the two wave-wide sums of one 64-value vector: out[0..63] = MFMA form per lane, out[64..127] = DPP form per lane
@@ -448,6 +479,7 @@ static int fdm_setup() {
     for (int kz = 0; kz < 8; ++kz)
       for (int kx = 0; kx < 8; ++kx) invD[ky * 64 + kz * 8 + kx] = 1.0 / (lam[kx] + lam[ky] + lam[kz]);
   CUP3D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(cQ), Q, sizeof Q));
+  CUP3D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(cLam), lam, sizeof lam));
   CUP3D_HIP(hipMalloc((void **)&g_invD, sizeof invD));
   CUP3D_HIP(hipMemcpy(g_invD, invD, sizeof invD, hipMemcpyHostToDevice));
   return CUP3D_OK;
@@ -536,8 +568,11 @@ int launch_precond(Sim *s, const double *in, double *out, bool want_sums) {
   return CUP3D_OK;
 }
 
+static int launch_precond_fdm_helm(Sim *s, const double *in, double *out, const HelmholtzOp &op);  // at the end of poisson.hip (see k_precond_fdm_helm)
+
 int launch_precond_diffusion(Sim *s, const double *in, double *out, const HelmholtzOp &op) {
   GridDev g = s->gdev();
+  if (s->diffusion_block_solver == 1) return launch_precond_fdm_helm(s, in, out, op);  // cup3d_diffusion_set_block_solver: the direct solve
   ProfileScope ps("diffusion_block_cg");
   if (s->block_solver != 2) hipLaunchKernelGGL((k_precond<true, true, kCgProduction>), dim3(launch_groups(g)), dim3(64), 0, stream(), g, in, out, (double *)nullptr, op.nu, op.dt, (int *)nullptr);
   else hipLaunchKernelGGL((k_precond<false, true, 0>), dim3(launch_groups(g)), dim3(64), 0, stream(), g, in, out, (double *)nullptr, op.nu, op.dt, (int *)nullptr);

@@ -115,6 +115,7 @@ struct Sim {
   bool chi_path() const { return grid->nranks == 1 ? (obstacles_global == 1 || chi_nonzero) : obstacles_global != 0; }
   bool chi_conflict() const { return grid->nranks > 1 && obstacles_global == 0 && chi_nonzero; }
   int block_solver = 0;  // cup3d_poisson_params.block_solver of the running solve
+  int diffusion_block_solver = 0;  // cup3d_diffusion_set_block_solver: 0 = block CG, 1 = direct solve (launch_precond_diffusion)
   int scalar_bc_dir = -1;  // >= 0 while a Helmholtz solve of the implicit diffusion runs: domain-face rule of the scalar tiles
   // solver vectors (allocated on first solve), each [nb][512]
   Dev<double> sv[18];

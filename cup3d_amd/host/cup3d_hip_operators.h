@@ -297,6 +297,8 @@ private:
       MPI_Abort(sim.comm, 1);
     }
     CUP3D_HIP_CALL(cup3d_sim_create(grid, &dsim));
+    // the block solve of the implicit diffusion's Helmholtz solves: 0 block CG (default), 1 direct; a setting of the sim, so every rebuild sets it
+    if (const char *e = getenv("CUP3D_HIP_DIFFUSION_BLOCK_SOLVER")) CUP3D_HIP_CALL(cup3d_diffusion_set_block_solver(dsim, atoi(e)));
     signature.resize(2 * I.size());
     for (size_t i = 0; i < I.size(); ++i) {
       signature[2 * i] = I[i].level;

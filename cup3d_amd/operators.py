@@ -198,7 +198,7 @@ class SimulationData:
                  BC_x="freespace", BC_y="freespace", BC_z="freespace", uinf=(0.0, 0.0, 0.0), uMax_forced=0.0,
                  poissonTol=1e-6, poissonTolRel=1e-4, bMeanConstraint=1, poissonSolver="hip_iterative", rampup=100,
                  blockSolver=0, leaves=None, implicitDiffusion=False, diffusionTol=1e-6, diffusionTolRel=1e-4,
-                 rank=0, nranks=1, device=None, view=None):
+                 rank=0, nranks=1, device=None, view=None, diffusionBlockSolver=0):
         if device is not None or not capi._device_ready:
             capi.device_init(0 if device is None else device)
         self.bpdx, self.bpdy, self.bpdz = bpdx, bpdy, bpdz
@@ -228,6 +228,9 @@ class SimulationData:
         h = C.c_void_p()
         check(lib().cup3d_sim_create(self.grid.handle, C.byref(h)))
         self.handle = h
+        # the block solve of the implicit diffusion's Helmholtz solves -- 0: block CG as in the reference, 1: direct block solve
+        self.diffusionBlockSolver = int(diffusionBlockSolver)
+        check(lib().cup3d_diffusion_set_block_solver(h, self.diffusionBlockSolver))
         self.pressureSolver = None
         self.last_poisson = None
         self.Rtol, self.Ctol, self.levelMaxVorticity = 1e9, 0.0, levelMax   # -Rtol / -Ctol / -levelMaxVorticity (15340-15342)
@@ -346,7 +349,8 @@ class SimulationData:
                              uinf=self.uinf, uMax_forced=self.uMax_forced, poissonTol=self.PoissonErrorTol, poissonTolRel=self.PoissonErrorTolRel,
                              bMeanConstraint=self.bMeanConstraint, poissonSolver=self.poissonSolver, rampup=self.rampup,
                              blockSolver=self.blockSolver, implicitDiffusion=self.implicitDiffusion,
-                             diffusionTol=self.DiffusionErrorTol, diffusionTolRel=self.DiffusionErrorTolRel, **kw)
+                             diffusionTol=self.DiffusionErrorTol, diffusionTolRel=self.DiffusionErrorTolRel,
+                             diffusionBlockSolver=self.diffusionBlockSolver, **kw)
         new.dt, new.dt_old, new.time, new.step, new.coefU = self.dt, self.dt_old, self.time, self.step, self.coefU.copy()
         new.uMax_measured = self.uMax_measured
         return new

@@ -593,7 +593,8 @@ CUP3D_API int cup3d_compute_forces_resident_over_ranks(cup3d_sim_t *, const cup3
 /* Implicit diffusion: AdvectionDiffusionImplicit (main.cpp:7148-7157, 10030-10119), selected by -implicitDiffusion (15231-15232).
  * One call = euler(dt): KernelAdvect, the explicit-diffusion guess, KernelDiffusionRHS and one DiffusionSolver::solve per velocity
  * component.  `params`: tol / tol_rel = sim.DiffusionErrorTol / DiffusionErrorTolRel (15369-15370), max_iter; mean_constraint,
- * max_restarts and block_solver are ignored (DiffusionSolver has no mean constraint, no restart cap and its own block CG).
+ * max_restarts and block_solver are ignored (DiffusionSolver has no mean constraint, no restart cap and its own block CG; how that
+ * block preconditioner is evaluated is a setting of the sim, cup3d_diffusion_set_block_solver below).
  * results[3] (may be NULL): per-component solver statistics.  pres is used as scratch and restored; tmpV and lhs are clobbered.
  * KernelAdvect (9849-10029) updates vel IN PLACE in the reference while other blocks still build their ghosted tiles from it, so
  * the reference's own result depends on block order and thread timing; this implementation reads every tile from the velocity
@@ -610,6 +611,10 @@ CUP3D_API int cup3d_diffusion_rhs(cup3d_sim_t *);
 CUP3D_API int cup3d_diffusion_lhs(cup3d_sim_t *, int direction, double dt, double nu);
 /* diffusion_kernels::getZImplParallel (10534-10579): pres <- block-local CG solve with centre coefficient -6 - h^2/nu/dt, in place */
 CUP3D_API int cup3d_diffusion_preconditioner(cup3d_sim_t *, double dt, double nu);
+/* how DiffusionSolver's block preconditioner (diffusion_kernels::getZImplParallel, main.cpp:10534-10579) is evaluated by
+   cup3d_diffusion_preconditioner, cup3d_diffusion_solve and cup3d_advect_diffuse_implicit on this sim:
+   0 = the reference's block CG (default; association as today), 1 = direct solve by fast diagonalisation (exact to rounding). */
+CUP3D_API int cup3d_diffusion_set_block_solver(cup3d_sim_t *, int block_solver);
 /* DiffusionSolver::solve (6896-7146): right-hand side in lhs (clobbered), initial guess and result in pres */
 CUP3D_API int cup3d_diffusion_solve(cup3d_sim_t *, int direction, double dt, double nu, const cup3d_poisson_params *params, cup3d_poisson_result *result);
 /* ComputeVorticity::operator() (8726-8746, KernelVorticity 8624-8645): tmpV <- curl(vel); any mesh */

@@ -44,6 +44,11 @@ class RunStats(C.Structure):
                 ("host_wait_seconds", C.c_double), ("solver_iterations", C.c_long), ("field_bytes_uploaded", C.c_double), ("field_bytes_downloaded", C.c_double)]
 
 
+class MassFlux(C.Structure):
+    """cup3d_mass_flux"""
+    _fields_ = [("u_avg_msr", C.c_double), ("u_avg", C.c_double), ("delta_u", C.c_double), ("scale", C.c_double), ("re_tau", C.c_double)]
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_long), ("total_ms", C.c_double)]
 
@@ -163,6 +168,8 @@ SIGNATURES = {
     "cup3d_prolong": (C.c_int, [_vp, _vp, C.c_int]),
     "cup3d_tag_blocks": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, np.ctypeslib.ndpointer(dtype=np.int8, flags="C_CONTIGUOUS")]),
     "cup3d_compute_vorticity": (C.c_int, [_vp]),
+    "cup3d_compute_dissipation": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp]),
+    "cup3d_fix_mass_flux": (C.c_int, [_vp, C.c_double, C.c_double, C.c_double, _vp, _vp, C.POINTER(MassFlux)]),
     "cup3d_grad_chi_on_tmp": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int]),
     "cup3d_grad_chi_on_tmp_over_ranks": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_double, C.c_int]),
     "cup3d_grid_adapted_owners": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),

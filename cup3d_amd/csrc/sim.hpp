@@ -193,6 +193,9 @@ struct Sim {
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_h1 = nullptr, ev_h2 = nullptr, ev_m = nullptr;
   hipEvent_t ev_vc_pack = nullptr, ev_vc_done = nullptr;  // virtual communicator (tests): "my send buffer is packed" / "my copies are enqueued"
+  // cup3d_compute_dissipation / cup3d_fix_mass_flux (diagnostics.hip), made by the first call of either: h and origin of every local
+  // block [nb][4], and the blocks' rows of sums [nb + 1][20] (the last row: this rank's totals)
+  Dev<double> d_diag_geom, d_diag_rows;
 
   GridDev gdev(bool boundary_only = false, bool inner_only = false) const;
   GridDev gdev_list(const int32_t *list, unsigned n) const;  // the same over an explicit block list

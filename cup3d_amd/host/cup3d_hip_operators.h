@@ -389,6 +389,32 @@ public:
   }
 };
 
+// FixMassFlux::operator()(dt), main.cpp:12218-12248 (-bFixMassFlux 1): on the device while the velocity is resident there -- the mean of
+// u + uinf[0] and the parabolic correction of vel.u[0], cup3d_fix_mass_flux -- else the reference's own operator.  The library prints
+// nothing: the reference's five lines (12229-12234) are printed here, on rank 0, from the numbers it returns.
+// Installed only with CUP3D_HIP_MASSFLUX=1 (install()).
+class FixMassFluxHIP : public Operator {
+  std::shared_ptr<DeviceMirror> devp;
+  std::shared_ptr<Operator> cpu;
+
+public:
+  cup3d_mass_flux last;
+  FixMassFluxHIP(SimulationData &s, std::shared_ptr<DeviceMirror> d, std::shared_ptr<Operator> original) : Operator(s), devp(d), cpu(original), last() {}
+  void operator()(const Real dt) override {
+    if (!devp->vel_on_device) { (*cpu)(dt); return; }
+    const double extents[3] = {sim.extents[0], sim.extents[1], sim.extents[2]}, uinf[3] = {sim.uinf[0], sim.uinf[1], sim.uinf[2]};
+    CUP3D_HIP_CALL(cup3d_fix_mass_flux(devp->handle(), sim.uMax_forced, sim.nu, sim.dt, extents, uinf, &last));  // reTau reads sim.dt, 12226
+    if (sim.rank == 0) {
+      printf("Measured <Ux>_V = %25.16e,\n"
+             "target   <Ux>_V = %25.16e,\n"
+             "delta    <Ux>_V = %25.16e,\n"
+             "scale           = %25.16e,\n"
+             "Re_tau          = %25.16e,\n",
+             last.u_avg_msr, last.u_avg, last.delta_u, last.scale, last.re_tau);
+    }
+  }
+};
+
 // UpdateObstacles::operator()(dt), main.cpp:13812-13837, is the first host operator after the advection step that reads the
 // velocity -- in the blocks an obstacle covers only.  While the velocity is resident on the device this wrapper fetches exactly
 // those blocks, then runs the reference's own operator; Penalization (next in the pipeline) updates the same blocks on the host and
@@ -707,6 +733,7 @@ struct Installed {
   std::shared_ptr<DeviceMirror> mirror;
   std::shared_ptr<Operator> advdiff;  // AdvectionDiffusionHIP, or AdvectionDiffusionImplicitHIP with -implicitDiffusion 1
   std::shared_ptr<ExternalForcingHIP> forcing;
+  std::shared_ptr<FixMassFluxHIP> mass_flux;  // only with CUP3D_HIP_MASSFLUX=1
   std::shared_ptr<UpdateObstaclesHIP> update_obstacles;
   std::shared_ptr<PressureProjectionHIP> projection;
   std::shared_ptr<ComputeForcesHIP> forces;  // only with CUP3D_HIP_FORCES=1
@@ -720,7 +747,9 @@ struct Installed {
 // ExternalForcing (then run on the device too) or one of the obstacle operators: UpdateObstacles and Penalization touch the
 // velocity only in the blocks an obstacle covers, so those blocks alone make the round trip (UpdateObstaclesHIP fetches them,
 // PressureProjectionHIP sends them back); without obstacles both return immediately (13813-13814, 14327-14328).  With
-// FixMassFlux in between, every operator round-trips in full as before.
+// FixMassFlux in between, every operator round-trips in full as before -- unless CUP3D_HIP_MASSFLUX=1 (environment): FixMassFlux
+// (15236-15237) is then replaced by FixMassFluxHIP, which runs on the device while the velocity is resident there, and counts as a device
+// operator for this rule, so that a channel run (-bFixMassFlux 1) can stay resident.  Without the variable nothing changes.
 // CUP3D_HIP_FORCES=1 (environment): ComputeForces (15244) is replaced by ComputeForcesHIP as well; without it that entry of the
 // pipeline stays the reference's own.  CUP3D_HIP_CREATE=1: CreateObstacles (15230) is replaced by CreateObstaclesHIP in the same way.
 inline Installed install(SimulationData &sim, int resident = -1) {
@@ -730,12 +759,14 @@ inline Installed install(SimulationData &sim, int resident = -1) {
     const char *e = getenv("CUP3D_HIP_RESIDENT");
     resident = e ? atoi(e) : 0;
   }
+  const char *massflux_env = getenv("CUP3D_HIP_MASSFLUX");
+  const bool massflux = massflux_env && atoi(massflux_env) == 1;
   bool between = false, safe = true;
   for (auto &op : sim.pipeline) {
     if (std::dynamic_pointer_cast<AdvectionDiffusion>(op) || std::dynamic_pointer_cast<AdvectionDiffusionImplicit>(op)) between = true;
     else if (std::dynamic_pointer_cast<PressureProjection>(op)) between = false;
     else if (between && !(std::dynamic_pointer_cast<ExternalForcing>(op) || std::dynamic_pointer_cast<UpdateObstacles>(op) ||
-                          std::dynamic_pointer_cast<Penalization>(op)))
+                          std::dynamic_pointer_cast<Penalization>(op) || (massflux && std::dynamic_pointer_cast<FixMassFlux>(op))))
       safe = false;
   }
   r.mirror->resident = resident != 0 && safe;
@@ -762,6 +793,9 @@ inline Installed install(SimulationData &sim, int resident = -1) {
     } else if (r.mirror->resident && std::dynamic_pointer_cast<ExternalForcing>(op)) {
       r.forcing = std::make_shared<ExternalForcingHIP>(sim, r.mirror, op);
       op = r.forcing;
+    } else if (massflux && r.mirror->resident && std::dynamic_pointer_cast<FixMassFlux>(op)) {
+      r.mass_flux = std::make_shared<FixMassFluxHIP>(sim, r.mirror, op);
+      op = r.mass_flux;
     } else if (r.mirror->resident && std::dynamic_pointer_cast<UpdateObstacles>(op)) {
       r.update_obstacles = std::make_shared<UpdateObstaclesHIP>(sim, r.mirror, op);
       op = r.update_obstacles;

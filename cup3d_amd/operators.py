@@ -198,7 +198,7 @@ class SimulationData:
                  BC_x="freespace", BC_y="freespace", BC_z="freespace", uinf=(0.0, 0.0, 0.0), uMax_forced=0.0,
                  poissonTol=1e-6, poissonTolRel=1e-4, bMeanConstraint=1, poissonSolver="hip_iterative", rampup=100,
                  blockSolver=0, leaves=None, implicitDiffusion=False, diffusionTol=1e-6, diffusionTolRel=1e-4,
-                 rank=0, nranks=1, device=None, view=None, diffusionBlockSolver=0):
+                 rank=0, nranks=1, device=None, view=None, diffusionBlockSolver=0, bFixMassFlux=False, freqDiagnostics=100):
         if device is not None or not capi._device_ready:
             capi.device_init(0 if device is None else device)
         self.bpdx, self.bpdy, self.bpdz = bpdx, bpdy, bpdz
@@ -217,6 +217,8 @@ class SimulationData:
         self.BCx_flag, self.BCy_flag, self.BCz_flag = BC_x, BC_y, BC_z
         self.nu, self.CFL, self.uinf = float(nu), float(CFL), np.array(uinf, dtype=np.float64)
         self.uMax_forced, self.rampup = float(uMax_forced), int(rampup)
+        # -bFixMassFlux / -freqDiagnostics (main.cpp:15359, 15363)
+        self.bFixMassFlux, self.freqDiagnostics = bool(bFixMassFlux), int(freqDiagnostics)
         self.PoissonErrorTol, self.PoissonErrorTolRel, self.bMeanConstraint = poissonTol, poissonTolRel, bMeanConstraint
         self.poissonSolver = poissonSolver
         # -implicitDiffusion / -diffusionTol / diffusionTolRel (main.cpp:15368-15370)
@@ -350,7 +352,8 @@ class SimulationData:
                              bMeanConstraint=self.bMeanConstraint, poissonSolver=self.poissonSolver, rampup=self.rampup,
                              blockSolver=self.blockSolver, implicitDiffusion=self.implicitDiffusion,
                              diffusionTol=self.DiffusionErrorTol, diffusionTolRel=self.DiffusionErrorTolRel,
-                             diffusionBlockSolver=self.diffusionBlockSolver, **kw)
+                             diffusionBlockSolver=self.diffusionBlockSolver, bFixMassFlux=self.bFixMassFlux,
+                             freqDiagnostics=self.freqDiagnostics, **kw)
         new.dt, new.dt_old, new.time, new.step, new.coefU = self.dt, self.dt_old, self.time, self.step, self.coefU.copy()
         new.uMax_measured = self.uMax_measured
         return new
@@ -777,6 +780,55 @@ class ExternalForcing(Operator):
         check(lib().cup3d_external_forcing(s.handle, s.uMax_forced, s.nu, s.extents[d], dt))
 
 
+class FixMassFlux(Operator):
+    """FixMassFlux::operator()(dt), main.cpp:12218-12248: the measured mean of u + uinf[0] on the device, then the
+    parabolic correction of vel.u[0] in place (cup3d_fix_mass_flux).  Leaves the five numbers the reference prints in sim.mass_flux:
+    u_avg_msr, u_avg, delta_u, scale, re_tau.  A collective where the grid is spread over ranks."""
+
+    def __call__(self, dt):
+        s = self.sim
+        out = capi.MassFlux()
+        ext, uinf = np.array(s.extents, dtype=np.float64), np.ascontiguousarray(s.uinf, dtype=np.float64)
+        check(lib().cup3d_fix_mass_flux(s.handle, s.uMax_forced, s.nu, dt, ext.ctypes.data_as(C.c_void_p),
+                                        uinf.ctypes.data_as(C.c_void_p), C.byref(out)))
+        s.mass_flux = {k: float(getattr(out, k)) for k in ("u_avg_msr", "u_avg", "delta_u", "scale", "re_tau")}
+        return s.mass_flux
+
+
+class ComputeDissipation(Operator):
+    """ComputeDissipation::operator()(dt), main.cpp:10436-10447: every sim.freqDiagnostics steps the 20 flow integrals of KernelDissipation
+    (10347-10434) from the resident vel, pres and chi (cup3d_compute_dissipation), all-reduced where the grid is spread over ranks (then a
+    collective).  The reference drops them; here they stay in sim.diagnostics = {"step", "time", "qoi": ndarray[20]} (NAMES labels them)
+    and are returned.  block_sums=True also keeps this rank's per-block sums [nblocks][20] under "block_sums"."""
+
+    NAMES = ("vorticity_x", "vorticity_y", "vorticity_z", "linear_impulse_x", "linear_impulse_y", "linear_impulse_z",
+             "momentum_x", "momentum_y", "momentum_z", "angular_impulse_x", "angular_impulse_y", "angular_impulse_z",
+             "angular_momentum_x", "angular_momentum_y", "angular_momentum_z", "pressure_power", "viscous_power", "helicity",
+             "kinetic_energy", "vorticity_magnitude")
+
+    def __call__(self, dt=0, block_sums=False):
+        s = self.sim
+        if s.freqDiagnostics == 0 or s.step % s.freqDiagnostics:   # 10437
+            return None
+        return self.compute(block_sums)
+
+    def compute(self, block_sums=False):
+        """the integrals of the state as it stands, whatever the step"""
+        s = self.sim
+        qoi = np.zeros(20)
+        rows = np.zeros((s.nblocks, 20)) if block_sums else None
+        ext = np.array(s.extents, dtype=np.float64)
+        check(lib().cup3d_compute_dissipation(s.handle, s.nu, ext.ctypes.data_as(C.c_void_p), qoi.ctypes.data_as(C.c_void_p),
+                                              rows.ctypes.data_as(C.c_void_p) if block_sums else None))
+        s.diagnostics = {"step": s.step, "time": s.time, "qoi": qoi}
+        if block_sums:
+            s.diagnostics["block_sums"] = rows
+        return qoi
+
+
+NAMES = ComputeDissipation.NAMES
+
+
 class ComputeLHS(Operator):
     """ComputeLHS::operator()(dt), main.cpp:9273-9327: lhs <- A(pres)."""
 
@@ -882,7 +934,7 @@ class Simulation:
     """The time loop of struct Simulation restricted to the hot path (no obstacles, frozen mesh):
     calcMaxTimestep 15254-15305, advance 15306-15326, pipeline order of setupOperators 15229-15246."""
 
-    def __init__(self, sim, obstacle_operators=False, collisions=False, resident_obstacles=False, forces=False):
+    def __init__(self, sim, obstacle_operators=False, collisions=False, resident_obstacles=False, forces=False, diagnostics=False):
         """obstacle_operators: with sim.obstacles, put UpdateObstacles and Penalization between the forcing and PressureProjection
         (15235-15243) -- the resident obstacle step -- and, where sim.shapes is set (ObstacleShape list), CreateObstacles in front of
         everything.  Off by default: the caller then runs Penalization itself.
@@ -891,23 +943,25 @@ class Simulation:
         resident_obstacles: with obstacle_operators, UpdateObstacles, Penalization and PressureProjection's tmpV update read the blocks, chi
         and udef CreateObstacles leaves on the device instead of uploading them per obstacle (sets sim.resident_obstacles); the same
         pipeline and the same bits.  It needs sim.shapes, so that CreateObstacles runs in front of them.
-        forces: ComputeForces after PressureProjection, as setupOperators ends (15244), on the retained set: it needs resident_obstacles."""
+        forces: ComputeForces after PressureProjection, as setupOperators ends (15244), on the retained set: it needs resident_obstacles.
+        diagnostics: ComputeDissipation last (15245): every sim.freqDiagnostics steps the 20 flow integrals land in sim.diagnostics.
+        With sim.bFixMassFlux and sim.uMax_forced > 0, FixMassFlux takes ExternalForcing's place (15235-15240)."""
         if forces and not resident_obstacles:
             raise ValueError("forces=True needs resident_obstacles=True: ComputeForces in the pipeline reads the blocks CreateObstacles leaves on the device")
         if resident_obstacles and not (obstacle_operators and getattr(sim, "shapes", None)):
             raise ValueError("resident_obstacles=True needs obstacle_operators=True and sim.shapes (an ObstacleShape list): the operators "
                              "read the blocks CreateObstacles leaves on the device")
-        self._bind(sim, obstacle_operators, collisions, resident_obstacles, forces)
+        self._bind(sim, obstacle_operators, collisions, resident_obstacles, forces, diagnostics)
 
-    def _bind(self, sim, obstacle_operators, collisions, resident_obstacles, forces=False):
+    def _bind(self, sim, obstacle_operators, collisions, resident_obstacles, forces=False, diagnostics=False):
         """the operators on `sim`: what __init__ does, and adaptMesh / adaptMeshOverRanks again on the adapted SimulationData"""
         self.sim, self.obstacle_operators, self.collisions = sim, bool(obstacle_operators), bool(collisions)
-        self.resident_obstacles, self.forces = bool(resident_obstacles), bool(forces)
+        self.resident_obstacles, self.forces, self.diagnostics = bool(resident_obstacles), bool(forces), bool(diagnostics)
         if self.resident_obstacles or hasattr(sim, "resident_obstacles"):
             sim.resident_obstacles = self.resident_obstacles
         self.pipeline = [AdvectionDiffusionImplicit(sim) if sim.implicitDiffusion else AdvectionDiffusion(sim)]  # 15231-15234
-        if sim.uMax_forced > 0:
-            self.pipeline.append(ExternalForcing(sim))
+        if sim.uMax_forced > 0:   # 15235-15240
+            self.pipeline.append(FixMassFlux(sim) if sim.bFixMassFlux else ExternalForcing(sim))
         shapes = getattr(sim, "shapes", None)   # ObstacleShape list: CreateObstacles comes first, as in setupOperators (15230)
         if self.obstacle_operators and shapes:
             self.pipeline.insert(0, CreateObstacles(sim))
@@ -916,6 +970,8 @@ class Simulation:
         self.pipeline.append(PressureProjection(sim))
         if self.forces:
             self.pipeline.append(ComputeForces(sim))   # 15244
+        if self.diagnostics:
+            self.pipeline.append(ComputeDissipation(sim))   # 15245
 
     def adaptMesh(self, Rtol, Ctol):
         """Simulation::adaptMesh (15179-15194) without obstacles: vorticity -> tags -> ValidStates -> Adapt.  Replaces
@@ -927,7 +983,7 @@ class Simulation:
             GradChiOnTmp(s)(0)
         st = s.grid.valid_states(MeshAdaptation(Rtol, Ctol).Tag(s, "tmpV"))
         if (st != 0).any():
-            self._bind(s.adapted(st), self.obstacle_operators, self.collisions, self.resident_obstacles, self.forces)
+            self._bind(s.adapted(st), self.obstacle_operators, self.collisions, self.resident_obstacles, self.forces, self.diagnostics)
         return st
 
     def adaptMeshOverRanks(self, mesh, owner, rank, nranks, Rtol, Ctol, allgather):
@@ -949,7 +1005,7 @@ class Simulation:
         if not (st != 0).any():
             return st, mesh, owner
         new, new_mesh, new_owner = s.adapted_over_ranks(mesh, owner, st, rank, nranks)
-        self._bind(new, self.obstacle_operators, self.collisions, self.resident_obstacles, self.forces)
+        self._bind(new, self.obstacle_operators, self.collisions, self.resident_obstacles, self.forces, self.diagnostics)
         return st, new_mesh, new_owner
 
     def calcMaxTimestep(self):

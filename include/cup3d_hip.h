@@ -620,6 +620,20 @@ CUP3D_API int cup3d_diffusion_solve(cup3d_sim_t *, int direction, double dt, dou
 /* ComputeVorticity::operator() (8726-8746, KernelVorticity 8624-8645): tmpV <- curl(vel); any mesh */
 CUP3D_API int cup3d_compute_vorticity(cup3d_sim_t *);
 
+/* ComputeDissipation::operator() (main.cpp:10436-10447; KernelDissipation 10347-10434): the 20 integrals RDX[0..19] of vel, pres, chi;
+ * any mesh, one rank or a share / rank view (then incl. the SUM all-reduce of 10443).  block_sums: NULL or [nblocks][20], this rank's per-block sums.
+ * In the reference's order: vorticity integral x3, linear impulse x3, momentum x3, angular impulse x3, angular momentum x3 (about
+ * extents/2), pressure power, viscous power, helicity, kinetic energy, integral of |omega|.  The reference computes and drops them.
+ * Every summand is the reference's expression (hCube = pow(h, 3)); the sums are ordered: a block adds its cells in iz, iy, ix order onto
+ * 0.0, a rank its blocks in slot order onto 0.0, the ranks by the all-reduce -- the reference's one-thread result on a one-block grid.
+ * chi is read as it stands (zero unless written).  The first call of this or of cup3d_fix_mass_flux allocates (nblocks * 24 + 20) doubles. */
+CUP3D_API int cup3d_compute_dissipation(cup3d_sim_t *, double nu, const double extents[3], double qoi[20], double *block_sums);
+/* FixMassFlux::operator() (main.cpp:12199-12248): the mean of u + uinf[0] over the volume (avgUx_nonUniform 12199-12216, divided by the
+ * volume before the SUM all-reduce of 12224; same ordered sums as above, h*h*h here), then vel.u[0] += 6 * scale * y/H * (1 - y/H) in
+ * place, scale = 6 * (2/3 umax_forced - mean), H = extents[1].  Nothing is printed: *out (may be NULL) receives the numbers. */
+typedef struct { double u_avg_msr, u_avg, delta_u, scale, re_tau; } cup3d_mass_flux;   /* the five numbers of the printf at 12229-12234 */
+CUP3D_API int cup3d_fix_mass_flux(cup3d_sim_t *, double umax_forced, double nu, double dt, const double extents[3], const double uinf[3], cup3d_mass_flux *out);
+
 /* compute<ScalarLab>(GradChiOnTmp(sim), sim.chi) (main.cpp:15182, 8540-8600): tmpV (the vorticity left by cup3d_compute_vorticity) edited
  * from the resident chi on its tensorial [-2,3) tile -- blocks with an obstacle surface within reach are flagged (1e10), cells deep
  * inside a body cleared, vorticity capped on level levelMaxVorticity - 1.  With cup3d_compute_vorticity before and cup3d_tag_blocks
